@@ -29,8 +29,8 @@ int dgi_paged_prefill(const void* q, int q_stride, const void* k_cache, const vo
 int dgi_silu_mul(const void* gu, void* out, int T, int I, hipStream_t s);
 int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int M,
                     int N, int K, int nw, hipStream_t s);
-int dgi_mfma_gemm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, int epi,
-                  hipStream_t s);
+int dgi_mfma_gemm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, int swiglu,
+                  int sched, int streamk, int phases, int overlap, hipStream_t s);
 void dgi_set_gemm_cus(int cus);
 int dgi_gemm_split_timeouts(int reset);
 int dgi_mfma_gemm_norm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, int kind,
@@ -224,24 +224,28 @@ void skinny_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w,
 }
 
 // LDS-tiled MFMA GEMM (prefill / mixed steps): epi 0 out = x w^T; epi 1 out = SwiGLU with w = [gate; up].
-void mfma_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, int64_t epi) {
+// sched 3: the ping-pong kernel, steered by streamk (split-K policy: 0 auto, 1 off, 2 whenever), phases per
+// K tile (0 auto, 2, 4) and overlap; 0 / 1: the one-barrier-per-K-step kernel; 4: the half tile (epi 0).
+void mfma_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, int64_t epi, int64_t sched,
+               int64_t streamk, int64_t phases, bool overlap) {
   check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "mfma_gemm: 2-D operands");
   TORCH_CHECK(x.device() == w.device() && x.device() == out.device(), "mfma_gemm: operands on one device");
   TORCH_CHECK(x.stride(1) == 1 && out.stride(1) == 1 && w.is_contiguous(), "mfma_gemm: row-major operands");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K && out.size(0) == M, "mfma_gemm: shape mismatch");
-  TORCH_CHECK((epi & 15) <= 1 && ((epi >> 4) & 15) <= 4 && ((epi >> 8) & 3) <= 2 && ((epi >> 10) & 3) <= 2 && (epi >> 15) == 0,
-              "mfma_gemm: epi 0 (store) or 1 (SwiGLU), + 16 * schedule + 256 * stream-K mode");
-  TORCH_CHECK(((epi >> 4) & 15) != 4 || (epi & 15) == 0, "mfma_gemm: schedule 4 (half tile) is a plain GEMM");
-  TORCH_CHECK(out.size(1) == ((epi & 15) == 1 ? N / 2 : N), "mfma_gemm: output columns");
+  TORCH_CHECK((epi == 0 || epi == 1) && streamk >= 0 && streamk <= 2 && (phases == 0 || phases == 2 || phases == 4),
+              "mfma_gemm: epi 0 (store) or 1 (SwiGLU), streamk 0-2, phases 0, 2 or 4");
+  TORCH_CHECK(sched == 0 || sched == 1 || sched == 3 || sched == 4, "mfma_gemm: schedule 0, 1, 3 or 4");
+  TORCH_CHECK(sched != 4 || epi == 0, "mfma_gemm: schedule 4 (half tile) is a plain GEMM");
+  TORCH_CHECK(out.size(1) == (epi == 1 ? N / 2 : N), "mfma_gemm: output columns");
   TORCH_CHECK(N % 256 == 0 && K % 64 == 0 && x.stride(0) % 8 == 0 && out.stride(0) % 4 == 0,
               "mfma_gemm: N%256, K%64, ldx%8, ldy%4");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
               reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0, "mfma_gemm: operand alignment");
   TORCH_CHECK((int64_t)M * x.stride(0) < (1LL << 31), "mfma_gemm: activation too large for 32-bit offsets");
   check_rc(dgi_mfma_gemm(x.data_ptr(), (int)x.stride(0), w.data_ptr(), out.data_ptr(), (int)out.stride(0), (int)M,
-                         (int)N, (int)K, (int)epi, cur_stream()),
+                         (int)N, (int)K, (int)epi, (int)sched, (int)streamk, (int)phases, overlap, cur_stream()),
            "mfma_gemm");
 }
 
@@ -595,7 +599,8 @@ TORCH_LIBRARY(dgi, m) {
         "Tensor? tree_mask, int tree_n, int tile_rows=128) -> ()");
   m.def("silu_mul(Tensor(a!) out, Tensor gu) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
-  m.def("mfma_gemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0) -> ()");
+  m.def("mfma_gemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, int sched=3, int streamk=0, int phases=0, "
+        "bool overlap=True) -> ()");
   m.def("mfma_gemm_norm(Tensor(a!) out, Tensor x, Tensor w, int kind, Tensor(b!) ss, float inv_k, float eps, "
         "int phases=0) -> ()");
   m.def("mfma_gemm_norm_rope(Tensor(a!) out, Tensor x, Tensor w, Tensor ss, float inv_k, float eps, "

@@ -1,12 +1,36 @@
 // dgi/csrc/mfma_gemm.hip — LDS-tiled MFMA GEMM for prefill / mixed-step projections
-// (SURVEY K3/K8/K11), with an optional fused SwiGLU epilogue.
+// (SURVEY K3/K8/K11), with fused SwiGLU, residual, RMSNorm and RoPE epilogues.
 //
 //   epi 0:  Y[M, N]  = X[M, K] · W[N, K]^T
 //   epi 1:  Y[M, I]  = silu(X · Wg^T) * (X · Wu^T)   with W = [Wg; Wu] (2I x K, the
 //           layout of the model's fused gate_up weight)
+//   epi 2:  Y += X · W^T in place, with the row statistics of the next RMSNorm
+//   epi 3 / 4:  epi 0 / 1 of the RMS-normalised X (row scale applied to the accumulators)
+//   epi 5:  epi 3 of the fused qkv weight, with RoPE and the paged-KV write
+//   (epi 2-5 in full: see EpiKind)
 //
 // bf16 in/out, fp32 accumulate.  Written for gfx950 (CDNA4), one 512-thread
-// workgroup (8 waves) per CU:
+// workgroup (8 waves) per CU.  Two kernels share the tile, the LDS image and the
+// fragment map below (the interface names them by schedule number: 0 and 1 the
+// simple kernel's SCHED, 3 ping-pong, 4 the half tile):
+//
+//  * mfma_gemm_pp_kernel<EPI, PH>, the ping-pong kernel: what every caller gets.
+//    Epilogue kinds 0-5.  The two wave groups of a SIMD alternate between a
+//    section of fragment reads + staging loads and a section of MFMAs, 2 or 4
+//    such phases per K tile (PH), staging loads 3-6 phases in flight.  A block
+//    owns one output tile, or — persistent launches — a split-K piece of a tile
+//    and then whole tiles, the next tile's first loads issued under the current
+//    tile's epilogue.  Schedule, phase tables and work decomposition: the
+//    comment above PPArgs; host-side choice of the decomposition: launch_pp.
+//  * mfma_gemm_kernel<EPI, SCHED>, the simple kernel, epilogue kinds 0 and 1: one
+//    tile per block, one barrier per K step, in compiler order (SCHED 0) or with
+//    the memory instructions interleaved between the MFMAs (SCHED 1).  SCHED 1
+//    runs when K does not fit the ping-pong kernel (K % 128 != 0 or K < 256) or
+//    when the caller asks for it; the tests use it as the bit-exact reference
+//    that screens the ping-pong kernel for races.
+//
+// (mfma_gemm_half_kernel is a 128 x 128 variant of the simple kernel, measured
+// slower and run only on request.)  Common to both:
 //
 //  * 256 x 256 output tile, K step 64, two LDS stages of X and W tiles
 //    (2 x 64 KB): the whole 160 KB LDS budget goes to one deep tile, so every
@@ -22,18 +46,13 @@
 //    operand, so each lane ends up with 4 consecutive output COLUMNS of one
 //    row (8-byte stores) — and, for SwiGLU, with the gate and up values of
 //    the same column in the same lane and register;
-//  * one barrier per K step (behind an explicit vmcnt(0): hipcc does not wait
-//    for global_load_lds before a barrier on its own): fragments of k-half 1 are read while the
-//    MFMAs of k-half 0 run, the barrier retires the next stage's loads and
-//    everyone's reads of the current stage, then the stage after next is
-//    issued into the stage just consumed while k-half 1's MFMAs run;
 //  * XCD-aware tile order: blocks that share an XCD (b % 8) take a
 //    contiguous run of tiles, M-fastest, so the 8 row tiles that reuse one
 //    W tile run side by side on one L2.
 //
-// Requirements (checked by the host): N % 256 == 0 (epi 1: I % 128 == 0),
-// K % 64 == 0, ldx % 8 == 0, ldy % 4 == 0.  Any M: rows past M are clamped
-// on load and skipped on store.
+// Requirements (checked by the host): N % 256 == 0 (epi 1 / 4: I % 128 == 0),
+// K % 64 == 0 (epi 2-5: K % 128 == 0 and K >= 256), ldx % 8 == 0, ldy % 4 == 0
+// (epi 5: ldy % 8).  Any M: rows past M are clamped on load and skipped on store.
 #include "common.h"
 
 #include <type_traits>
@@ -75,7 +94,7 @@ __device__ __forceinline__ void store_pair16(uint16_t* yrow, int n0, int g, cons
   *(uint4*)(yrow + n0 + 16 * (g & 1) + 4 * (g & 2)) = v;
 }
 
-// Epilogue kinds of the ping-pong kernel (the other schedules take 0 and 1):
+// Epilogue kinds of the ping-pong kernel (the simple kernel takes 0 and 1):
 //   0 plain store;  1 SwiGLU over [gate; up];
 //   2 residual:  Y <- Y + acc in place (Y is the residual stream), and the tile's per-row sum of
 //     squares of the new bf16 values to ss[m * ss_ld + tn] — the partial RMS statistics of the
@@ -214,6 +233,12 @@ __device__ __forceinline__ void epilogue_res(const f32x4 (&acc)[8][4], uint16_t*
     ss[(size_t)(m0 + t) * ss_ld + tn] = ((ssl[t] + ssl[256 + t]) + ssl[512 + t]) + ssl[768 + t];
 }
 
+// ---------------------------------------------------------------------------
+// The simple kernel (see the file header): one tile per block, two LDS stages, one barrier per
+// K step.  SCHED 1 (interleaved) takes the K the ping-pong kernel cannot (K % 128 != 0 or
+// K < 256) and is the bit-exact reference the tests screen the ping-pong kernel's races against
+// (each accumulator sums its K steps in the same order); SCHED 0 is the same loop in compiler
+// order.  EPI 0 or 1.
 template <int EPI, int SCHED>
 __global__ __launch_bounds__(512) void mfma_gemm_kernel(const uint16_t* __restrict__ X, int ldx,
                                                          const uint16_t* __restrict__ W,
@@ -486,153 +511,7 @@ __global__ __launch_bounds__(256) void mfma_gemm_half_kernel(const uint16_t* __r
 }
 
 // ---------------------------------------------------------------------------
-// Ring schedule (sched 2): the K loop advances in 32-deep sub-steps through a
-// ring of four 32 KB LDS slots (X 256 x 32 and W 256 x 32, 64-byte rows).
-// Sub-step u computes on fragments of u already in registers, reads u + 1's
-// fragments, and refills the slot u itself came from with u + 4 — so three
-// sub-steps of loads stay in flight across every barrier (counted
-// s_waitcnt vmcnt(8), never 0 in the steady state, raw s_barrier) and each
-// sub-step's 4 global_load_lds, 12 ds_read_b128 and 32 MFMAs are issued
-// interleaved.  64-byte rows: chunk c of row r holds k-chunk c ^ f((r >> 2) & 3)
-// with f = {0, 2, 3, 1}, conflict-free for the ds_read_b128 lane groups.
-template <int EPI>
-__global__ __launch_bounds__(512) void mfma_gemm_ring_kernel(const uint16_t* __restrict__ X, int ldx,
-                                                              const uint16_t* __restrict__ W,
-                                                              uint16_t* __restrict__ Y, int ldy, int M, int I,
-                                                              int K, int tiles_m, int tiles_total) {
-  constexpr int kSlot = 32768;        // X 16 KB + W 16 KB
-  constexpr int kHalf = 16384;
-  __shared__ __attribute__((aligned(16))) char smem[4 * kSlot];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = tid >> 6;
-  const int wm = w >> 2, wn = w & 3;
-
-  const int b = blockIdx.x;
-  const int xcd = b & 7, li = b >> 3;
-  const int q8 = tiles_total >> 3, r8 = tiles_total & 7;
-  const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + li;
-  const int tm = t % tiles_m, tn = t / tiles_m;
-  const int m0 = tm * kBM;
-
-  // staging: instruction i covers tile rows 128 i + (tid >> 2), 16-byte chunk tid & 3
-  const int rq = tid >> 2;
-  const int quad = (tid >> 4) & 3;
-  const int lc = (tid & 3) ^ ((0x1320 >> (quad * 4)) & 3);
-  const int xq = m0 + rq;
-  const uint16_t* const xsrc = X + lc * 8;
-  int wrow0, wstep;
-  if (EPI == 1) {            // tile row r -> wave column r >> 6; 32 gate rows then the 32 matching up rows
-    const int qq = rq & 63;
-    wrow0 = tn * 128 + (rq >> 6) * 32 + (qq < 32 ? qq : I + qq - 32);
-    wstep = 64;              // +128 tile rows = +2 wave columns = +64 weight rows
-  } else {
-    wrow0 = tn * 256 + rq;
-    wstep = 128;
-  }
-  const uint16_t* const wsrc = W + (size_t)wrow0 * K + lc * 8;
-  const size_t wslab = (size_t)wstep * K;
-  char* const lds_x = smem + w * 1024;
-  char* const lds_w = smem + kHalf + w * 1024;
-
-  auto issue = [&](int u) {
-    const int k0 = u * 32;
-    const int slot = (u & 3) * kSlot;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      glds16(xsrc + min(xq + i * 128, M - 1) * ldx + k0, lds_x + slot + i * 8192);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) glds16(wsrc + i * wslab + k0, lds_w + slot + i * 8192);
-  };
-
-  const int r16 = lane & 15;
-  const int ph = ((lane >> 4) ^ ((0x1320 >> (((lane >> 2) & 3) * 4)) & 3)) * 16;
-  const int xbase = (wm * 128 + r16) * 64 + ph;
-  const int wbase = kHalf + (wn * 64 + r16) * 64 + ph;
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  bf16x8 xa[8], wa[4], xb[8], wb[4];
-  auto read = [&](int u, bf16x8* xf, bf16x8* wf) {
-    const char* s = smem + (u & 3) * kSlot;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wf[j] = *(const bf16x8*)(s + wbase + j * 1024);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) xf[i] = *(const bf16x8*)(s + xbase + i * 1024);
-  };
-  auto mma = [&](const bf16x8* xf, const bf16x8* wf) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-  };
-  // steady-state sub-step (u + 4 < nu): compute on (xc, wc) = fragments of u, read u + 1 into
-  // (xn, wn_), refill slot u with u + 4 — branch-free, so the interleave below is one region
-  auto steady = [&](int u, bf16x8* xc, bf16x8* wc, bf16x8* xn, bf16x8* wn_) {
-    // the refill goes first: each global_load_lds rewrites M0, and hipcc waits for every
-    // outstanding LDS op before an M0 write, so issued behind the fragment reads it would
-    // serialise them
-    issue(u + 4);
-    read(u + 1, xn, wn_);
-    mma(xc, wc);
-    __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // slot u + 2 landed; u + 3, u + 4 in flight
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  // the last (up to 4) sub-steps: no refills, the in-flight slots drain
-  auto tail = [&](int u, int nu, bf16x8* xc, bf16x8* wc, bf16x8* xn, bf16x8* wn_) {
-    if (u + 1 < nu) read(u + 1, xn, wn_);
-    mma(xc, wc);
-    __builtin_amdgcn_sched_barrier(0);
-    if (u + 3 < nu)
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  const int nu = K / 32;
-  for (int u = 0; u < 4 && u < nu; ++u) issue(u);
-  // slots 0 and 1 landed (2 and 3 may still be in flight)
-  if (nu >= 4)
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  read(0, xa, wa);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();          // every wave holds slot 0 in registers: it may be refilled
-  __builtin_amdgcn_sched_barrier(0);
-  // nu is even (K % 64 == 0): steady pairs while both sub-steps refill, then drain in pairs
-  int u = 0;
-  for (; u + 5 < nu; u += 2) {
-    steady(u, xa, wa, xb, wb);
-    steady(u + 1, xb, wb, xa, wa);
-  }
-  for (; u < nu; u += 2) {
-    tail(u, nu, xa, wa, xb, wb);
-    tail(u + 1, nu, xb, wb, xa, wa);
-  }
-  epilogue<EPI>(acc, Y, ldy, M, m0, tn, wm, wn, lane);
-}
-
-// ---------------------------------------------------------------------------
-// Ping-pong schedule (sched 3).  Same tile, LDS image and fragment map as the
+// The ping-pong kernel.  Same tile, LDS image and fragment map as the simple
 // kernel above, but each K tile runs as 4 phases of 16 MFMAs per wave and the two
 // wave groups of a SIMD (waves 0-3: rows 0-127, waves 4-7: rows 128-255) are
 // staggered by one barrier: while one wave of a SIMD issues its fragment reads
@@ -893,16 +772,13 @@ __device__ __forceinline__ void drive(const PPArgs& a, char* smem, Pro&& prologu
   }
 }
 
-// PRIO: 0 = s_setprio 1 around each MFMA cluster (keeps hipcc from moving MFMAs across the
-// barriers; the instructions themselves are near free); 1 = static s_setprio 1 for waves 4-7
-// (the second-dispatched half) and no per-cluster flips; 2 = no s_setprio.
 // PH: phases per K tile, 4 (16 MFMAs per section, the table above) or 2 (32 MFMAs per
 // section, half the barrier hand-offs):
 //
 //   phase  reads             MFMAs          staging                       wait before the barrier
 //   0      Xa, Wa, Wb (16)   Xa x (Wa, Wb)  W0-3, X2 of t+1               vmcnt(6): X1, X3 of t landed
 //   1      Xb (8)            Xb x (Wa, Wb)  X3, X1 of t+1, X0 of t+2      vmcnt(3): all but X3, X1 of t+1
-template <int EPI, int PRIO, int PH>
+template <int EPI, int PH>
 __global__ __launch_bounds__(512) void mfma_gemm_pp_kernel(PPArgs a) {
   // EPI 2: per-wave row partials of the sum of squares; EPI 3 / 4: two slots of the tile's rstd
   // (slot per work item: a fast wave may start the next item while others still store this one).
@@ -948,8 +824,10 @@ __global__ __launch_bounds__(512) void mfma_gemm_pp_kernel(PPArgs a) {
       f[j][1] = *(const bf16x8*)(s + j * 2048 + ph1);
     }
   };
+  // s_setprio 1 around each MFMA cluster keeps hipcc from moving MFMAs across the barriers (the
+  // instructions themselves are near free)
   auto mma = [&](int i0, int j0, const bf16x8 (&xf)[4][2], const bf16x8 (&wf)[2][2]) {
-    if constexpr (PRIO == 0) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -957,11 +835,8 @@ __global__ __launch_bounds__(512) void mfma_gemm_pp_kernel(PPArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           acc[i0 + i][j0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][h], xf[i][h], acc[i0 + i][j0 + j], 0, 0, 0);
-    if constexpr (PRIO == 0) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
   };
-  if constexpr (PRIO == 1) {
-    if (wm == 1) __builtin_amdgcn_s_setprio(1);
-  }
   auto barrier = [&]() {
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("" ::: "memory");
@@ -1252,39 +1127,51 @@ int sk_timeouts(bool reset) {
 // second round.  Set by the host around such a step (dgi_set_gemm_cus).
 int g_cu_limit = 0;
 
-// skmode 0: whole tiles only; 1: hybrid split-K when the tiles leave the last wave at most half
-// full (and fewer than 8 full waves); 2: hybrid whenever tiles % CUs leaves room for 2 splits
-struct NormArgs {
-  float* ss = nullptr;
-  int ss_ld = 0;
-  float inv_k = 0.f, eps = 0.f;
-  const int* pos = nullptr;
-  const float* cs = nullptr;
-  const int* slots = nullptr;
-  uint16_t* kc = nullptr;
-  uint16_t* vc = nullptr;
-  int qcols = 0, kvcols = 0, nkv = 0, bs = 0;
+// The 256 x 256 output tiles of an [M, N] problem (swiglu: N = 2 I rows of W give I output
+// columns, 128 per tile)
+struct Tiling {
+  int I, tiles_m, total;
 };
 
+Tiling tiling(int M, int N, bool swiglu) {
+  const int I = swiglu ? N / 2 : 0;
+  const int tiles_m = (M + kBM - 1) / kBM;
+  return Tiling{I, tiles_m, tiles_m * (swiglu ? I / 128 : N / 256)};
+}
+
+// Phases per K tile: `phases` 2 or 4 asks for one; 0 takes 2 up to 10 row tiles (M <= 2560: the
+// 2-phase body measured 2-4 % faster there) and 4 above (its deeper prefetch wins at M = 4096)
+int pick_phases(int phases, int M) { return (phases == 2 || (phases == 0 && M <= 2560)) ? 2 : 4; }
+
+// The operands of an [M, K] x [N, K]^T problem; every other field zero (launch_pp fills the
+// decomposition, the fused-norm entry points their epilogue's fields)
+PPArgs pp_problem(const void* x, int ldx, const void* w, void* y, int ldy, int M, int K) {
+  PPArgs a{};
+  a.X = (const uint16_t*)x;
+  a.W = (const uint16_t*)w;
+  a.Y = (uint16_t*)y;
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.M = M;
+  a.K = K;
+  return a;
+}
+
+// skmode 0: whole tiles only; 1: hybrid split-K when the tiles leave the last wave at most half
+// full (and fewer than 8 full waves); 2: hybrid whenever tiles % CUs leaves room for 2 splits.
+// overlap false: the next tile's prologue after the epilogue, whole waves of tiles not persistent.
 template <int EPI>
-void launch_pp(const void* x, int ldx, const void* w, void* y, int ldy, int M, int I, int K, int tiles_m, int total,
-               int skmode, int prio, hipStream_t s, const NormArgs& na = NormArgs{}) {
-  decltype(&mfma_gemm_pp_kernel<EPI, 0, 2>) kern;
-  if constexpr (EPI >= 2)       // the fused-norm epilogues: default priority scheme only
-    kern = (prio & 4) ? mfma_gemm_pp_kernel<EPI, 0, 2> : mfma_gemm_pp_kernel<EPI, 0, 4>;
-  else
-    kern = (prio & 4) ? (prio & 3) == 1   ? mfma_gemm_pp_kernel<EPI, 1, 2>
-                        : (prio & 3) == 2 ? mfma_gemm_pp_kernel<EPI, 2, 2>
-                                          : mfma_gemm_pp_kernel<EPI, 0, 2>
-                      : (prio & 3) == 1   ? mfma_gemm_pp_kernel<EPI, 1, 4>
-                      : (prio & 3) == 2   ? mfma_gemm_pp_kernel<EPI, 2, 4>
-                                          : mfma_gemm_pp_kernel<EPI, 0, 4>;
+void launch_pp(PPArgs a, int N, int skmode, int phases, bool overlap, hipStream_t s) {
+  const auto kern = pick_phases(phases, a.M) == 2 ? mfma_gemm_pp_kernel<EPI, 2> : mfma_gemm_pp_kernel<EPI, 4>;
+  const Tiling t = tiling(a.M, N, EpiKind<EPI>::swiglu);
+  const int total = t.total;
+  a.I = t.I;
+  a.tiles_m = t.tiles_m;
+  a.tiles_total = total;
   // EPI 2 reads the tile it stores (in place) and EPI 5 stages its tile through the staging LDS: no
   // overlap of the next tile's loads with their epilogues
-  PPArgs a{(const uint16_t*)x, (const uint16_t*)w, (uint16_t*)y, nullptr, nullptr, ldx, ldy, M, I, K, tiles_m, total,
-           0, 0, 0, 0, !(prio & 8) && EPI != 2 && EPI != 5, na.ss, na.ss_ld, na.inv_k, na.eps,
-           na.pos, na.cs, na.slots, na.kc, na.vc, na.qcols, na.kvcols, na.nkv, na.bs};
-  const int nt = K / kBK;
+  a.ovl = overlap && EPI != 2 && EPI != 5;
+  const int nt = a.K / kBK;
   SkWorkspace* sk = ((skmode || a.ovl) && nt >= 8) ? sk_workspace(s) : nullptr;
   if (sk) {
     const int P = (g_cu_limit >= 8 && g_cu_limit < sk->P) ? (g_cu_limit & ~7) : sk->P;
@@ -1312,27 +1199,14 @@ void launch_pp(const void* x, int ldx, const void* w, void* y, int ldy, int M, i
 }
 
 template <int EPI, int SCHED>
-void launch(const void* x, int ldx, const void* w, void* y, int ldy, int M, int I, int K, int tiles_m, int total,
-            int skmode, int prio, hipStream_t s) {
-  if (SCHED == 3)
-    launch_pp<EPI>(x, ldx, w, y, ldy, M, I, K, tiles_m, total, skmode, prio, s);
-  else if (SCHED == 2)
-    mfma_gemm_ring_kernel<EPI><<<dim3(total), 512, 0, s>>>((const uint16_t*)x, ldx, (const uint16_t*)w,
-                                                          (uint16_t*)y, ldy, M, I, K, tiles_m, total);
-  else
-    mfma_gemm_kernel<EPI, SCHED><<<dim3(total), 512, 0, s>>>((const uint16_t*)x, ldx, (const uint16_t*)w,
-                                                            (uint16_t*)y, ldy, M, I, K, tiles_m, total);
+void launch_simple(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, hipStream_t s) {
+  const Tiling t = tiling(M, N, EPI == 1);
+  mfma_gemm_kernel<EPI, SCHED><<<dim3(t.total), 512, 0, s>>>((const uint16_t*)x, ldx, (const uint16_t*)w,
+                                                            (uint16_t*)y, ldy, M, t.I, K, t.tiles_m, t.total);
 }
 
 }  // namespace
 
-// epi & 1: 0 = Y[M, N] = X W^T with N = rows of W; 1 = Y[M, I] = SwiGLU with W = [gate; up] (2I rows).
-// epi >> 4: K-loop schedule (0 = compiler order, 1 = interleaved, 2 = 4-slot ring of 32-deep sub-steps,
-// 3 = ping-pong wave groups, 4 phases per K tile, 4 = 128 x 128 half tile, epi 0 only).  (epi >> 8) & 3: stream-K policy of schedule 3
-// (0 = auto, 1 = off, 2 = whenever the tiles leave the last wave part-empty).  (epi >> 10) & 3:
-// s_setprio variant of schedule 3, (epi >> 12) & 1: two 32-MFMA phases per K tile, (epi >> 13) & 1:
-// four 16-MFMA phases (default: two up to M = 2560, see mfma_gemm_pp_kernel), (epi >> 14) & 1: no
-// cross-tile overlap (next tile's prologue after the epilogue; whole waves of tiles not persistent).
 extern "C" void dgi_set_gemm_cus(int cus) { g_cu_limit = cus; }
 
 extern "C" int dgi_gemm_split_timeouts(int reset) { return sk_timeouts(reset != 0); }
@@ -1347,22 +1221,12 @@ extern "C" int dgi_mfma_gemm_norm(const void* x, int ldx, const void* w, void* y
     return -3;
   if (kind == 2 && ss_ld < N / 256) return -3;
   if (kind != 2 && (ss_ld % 8 || ss_ld > 32)) return -3;
-  int prio = (phases == 2 || (phases == 0 && M <= 2560)) ? 4 : 0;
-  const int I = kind == 4 ? N / 2 : 0;
-  const int tiles_n = kind == 4 ? I / 128 : N / 256;
-  const int tiles_m = (M + kBM - 1) / kBM;
-  const int total = tiles_m * tiles_n;
-  NormArgs na;
-  na.ss = ss;
-  na.ss_ld = ss_ld;
-  na.inv_k = inv_k;
-  na.eps = eps;
-  if (kind == 2)
-    launch_pp<2>(x, ldx, w, y, ldy, M, I, K, tiles_m, total, 1, prio, s, na);
-  else if (kind == 3)
-    launch_pp<3>(x, ldx, w, y, ldy, M, I, K, tiles_m, total, 1, prio, s, na);
-  else
-    launch_pp<4>(x, ldx, w, y, ldy, M, I, K, tiles_m, total, 1, prio, s, na);
+  PPArgs a = pp_problem(x, ldx, w, y, ldy, M, K);
+  a.ss = ss;
+  a.ss_ld = ss_ld;
+  a.inv_k = inv_k;
+  a.eps = eps;
+  (kind == 2 ? launch_pp<2> : kind == 3 ? launch_pp<3> : launch_pp<4>)(a, N, 1, phases, true, s);
   DGI_CHECK_LAUNCH();
   return 0;
 }
@@ -1379,33 +1243,34 @@ extern "C" int dgi_mfma_gemm_norm_rope(const void* x, int ldx, const void* w, vo
   if (K % (2 * kBK) || K < 4 * kBK || ldx % 8 || ldy % 8 || N % 256 || !ss || ss_ld % 8 || ss_ld > 32 || ss_ld <= 0)
     return -3;
   if ((nh * 128) % 256 || (nkv * 128) % 256 || N != (nh + 2 * nkv) * 128 || block_size <= 0) return -3;
-  int prio = (phases == 2 || (phases == 0 && M <= 2560)) ? 4 : 0;
-  const int tiles_m = (M + kBM - 1) / kBM;
-  const int total = tiles_m * (N / 256);
-  NormArgs na;
-  na.ss = ss;
-  na.ss_ld = ss_ld;
-  na.inv_k = inv_k;
-  na.eps = eps;
-  na.pos = pos;
-  na.cs = cos_sin;
-  na.slots = slots;
-  na.kc = (uint16_t*)k_cache;
-  na.vc = (uint16_t*)v_cache;
-  na.qcols = nh * 128;
-  na.kvcols = nkv * 128;
-  na.nkv = nkv;
-  na.bs = block_size;
-  launch_pp<5>(x, ldx, w, y, ldy, M, 0, K, tiles_m, total, 1, prio, s, na);
+  PPArgs a = pp_problem(x, ldx, w, y, ldy, M, K);
+  a.ss = ss;
+  a.ss_ld = ss_ld;
+  a.inv_k = inv_k;
+  a.eps = eps;
+  a.pos = pos;
+  a.cs = cos_sin;
+  a.slots = slots;
+  a.kc = (uint16_t*)k_cache;
+  a.vc = (uint16_t*)v_cache;
+  a.qcols = nh * 128;
+  a.kvcols = nkv * 128;
+  a.nkv = nkv;
+  a.bs = block_size;
+  launch_pp<5>(a, N, 1, phases, true, s);
   DGI_CHECK_LAUNCH();
   return 0;
 }
 
+// swiglu 0: Y[M, N] = X W^T with N = rows of W; 1: Y[M, I] = SwiGLU with W = [gate; up] (2 I rows).
+// sched: 3 = the ping-pong kernel (the simple kernel's schedule 1 when K does not fit it), 0 / 1 =
+// the simple kernel in compiler order / interleaved, 4 = the 128 x 128 half tile (swiglu 0 only).
+// Of the ping-pong kernel: streamk, the split-K policy (0 = auto, 1 = off, 2 = whenever the tiles
+// leave the last wave part-empty); phases per K tile (0 = auto, 2, 4: pick_phases); overlap 0 = no
+// cross-tile overlap.
 extern "C" int dgi_mfma_gemm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K,
-                             int epi, hipStream_t s) {
+                             int swiglu, int sched, int streamk, int phases, int overlap, hipStream_t s) {
   if (M <= 0) return 0;
-  const int swiglu = epi & 15;
-  int sched = (epi >> 4) & 15;
   if (sched == 4) {             // half tile: plain GEMM, N % 128
     if (swiglu || K % kBK || ldx % 8 || ldy % 4 || N % kHM) return -3;
     const int tiles_m = (M + kHM - 1) / kHM;
@@ -1416,23 +1281,18 @@ extern "C" int dgi_mfma_gemm(const void* x, int ldx, const void* w, void* y, int
     return 0;
   }
   if (K % kBK || ldx % 8 || ldy % 4 || N % 256) return -3;
-  const int skmode = ((epi >> 8) & 3) == 0 ? 1 : ((epi >> 8) & 3) == 1 ? 0 : 2;
-  int prio = ((epi >> 10) & 7) | (((epi >> 14) & 1) << 3);
-  // phases per K tile: (epi >> 13) & 1 forces 4; otherwise 2 up to 10 row tiles (M <= 2560: the
-  // 2-phase body measured 2-4 % faster there) and 4 above (its deeper prefetch wins at M = 4096)
-  if (!((epi >> 13) & 1) && !(prio & 4) && M <= 2560) prio |= 4;
-  if (swiglu > 1 || sched > 3) return -4;
+  if (swiglu < 0 || swiglu > 1 || (sched != 0 && sched != 1 && sched != 3) || streamk < 0 || streamk > 2 ||
+      (phases != 0 && phases != 2 && phases != 4))
+    return -4;
   if (sched == 3 && (K % (2 * kBK) || K < 4 * kBK)) sched = 1;   // ping-pong needs an even count of >= 4 K tiles
-  const int I = swiglu ? N / 2 : 0;
-  const int tiles_n = swiglu ? I / 128 : N / 256;
-  const int tiles_m = (M + kBM - 1) / kBM;
-  const int total = tiles_m * tiles_n;
-  if (swiglu)
-    (sched == 3 ? launch<1, 3> : sched == 2 ? launch<1, 2> : sched ? launch<1, 1> : launch<1, 0>)(
-        x, ldx, w, y, ldy, M, I, K, tiles_m, total, skmode, prio, s);
-  else
-    (sched == 3 ? launch<0, 3> : sched == 2 ? launch<0, 2> : sched ? launch<0, 1> : launch<0, 0>)(
-        x, ldx, w, y, ldy, M, I, K, tiles_m, total, skmode, prio, s);
+  if (sched == 0) {
+    (swiglu ? launch_simple<1, 0> : launch_simple<0, 0>)(x, ldx, w, y, ldy, M, N, K, s);
+  } else if (sched == 1) {
+    (swiglu ? launch_simple<1, 1> : launch_simple<0, 1>)(x, ldx, w, y, ldy, M, N, K, s);
+  } else {
+    const int skmode = streamk == 0 ? 1 : streamk == 1 ? 0 : 2;
+    (swiglu ? launch_pp<1> : launch_pp<0>)(pp_problem(x, ldx, w, y, ldy, M, K), N, skmode, phases, overlap != 0, s);
+  }
   DGI_CHECK_LAUNCH();
   return 0;
 }

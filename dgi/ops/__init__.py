@@ -576,9 +576,6 @@ def mfma_gemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
             and x.shape[1] % 64 == 0 and x.data_ptr() % 16 == 0 and x.shape[0] * x.stride(0) < (1 << 31))
 
 
-MFMA_SCHED = int(os.environ.get("DGI_MFMA_SCHED", "3"))
-
-
 def set_gemm_cus(cus: int) -> None:
     """CUs the MFMA GEMM's persistent / split-K launches size their grid for (0 = all of the
     device's): GEMMs issued on a CU-masked stream (two-batch overlap) set its CU count."""
@@ -597,26 +594,26 @@ def gemm_split_timeouts(reset: bool = False) -> int:
 
 
 def mfma_gemm(x: torch.Tensor, w: torch.Tensor, epi: int = 0, out: Optional[torch.Tensor] = None,
-              sched: Optional[int] = None, streamk: int = 0, prio: int = 0, phases: int = 0,
-              overlap: bool = True) -> torch.Tensor:
+              sched: int = 3, streamk: int = 0, phases: int = 0, overlap: bool = True) -> torch.Tensor:
     """Hand-written LDS-tiled MFMA GEMM (256x256 tiles, global_load_lds
     staging, XCD-aware tile order): ``epi`` 0 -> x @ w.T; 1 -> the fused
     SwiGLU of the MLP, silu(x @ gate.T) * (x @ up.T) with w = [gate; up],
     written once (no [M, 2I] intermediate and no separate silu_mul pass).
-    ``sched`` 3 is the ping-pong schedule; its ``streamk`` (split-K of the
+    ``sched`` 3 is the ping-pong kernel; its ``streamk`` (split-K of the
     last partial wave) policy: 0 auto, 1 off, 2 whenever it applies;
     ``phases`` per K tile: 0 auto (2 up to M = 2560, else 4), 2 or 4;
-    ``prio``: s_setprio variant (benchmarking); ``overlap`` False: no
-    cross-tile prologue / epilogue overlap (A/B)."""
+    ``overlap`` False: no cross-tile prologue / epilogue overlap (A/B).
+    ``sched`` 1, or a K that is no multiple of 128 or below 256: the
+    simple kernel (one barrier per K step), the bit-exact reference of
+    the ping-pong kernel; 0: that kernel in compiler order; 4: the
+    128 x 128 half tile (``epi`` 0; both kept for measurements)."""
     M = x.shape[0]
     N = w.shape[0] // 2 if epi == 1 else w.shape[0]
     if mfma_gemm_ok(x, w):
         load_native(required=True)
         if out is None:
             out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        _call("mfma_gemm", out, x, w, epi | ((MFMA_SCHED if sched is None else sched) << 4) | (streamk << 8)
-              | (prio << 10) | ((1 if phases == 2 else 0) << 12) | ((1 if phases == 4 else 0) << 13)
-              | ((0 if overlap else 1) << 14))
+        _call("mfma_gemm", out, x, w, epi, sched, streamk, phases, overlap)
         return out
     r = mfma_gemm_ref(x, w, epi)
     if out is not None:

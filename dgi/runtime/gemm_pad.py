@@ -22,7 +22,7 @@ GEMM) — and ``impl(rows)`` tells the model which one is faster at that row
 count on this GPU (``DGI_MFMA_GEMM=0`` keeps hipBLASLt everywhere, ``=force``
 the MFMA kernel wherever it applies).  The QKV and o projections get the same
 per-row-count choice (``proj_impl(rows)``, at the first grid point >= rows): with
-the ping-pong schedule and its split-K remainder (``ops.mfma_gemm`` sched 3) the
+the ping-pong kernel and its split-K remainder (``ops.mfma_gemm``) the
 hand-written kernel beats hipBLASLt on several of their row counts.
 """
 from __future__ import annotations

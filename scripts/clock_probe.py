@@ -29,7 +29,7 @@ def run():
         nbuf = max(2, int(1.2e9 // (N * 8192 * 2)))
         ws = [torch.randn(N, 8192, device=dev, dtype=bf) * 0.02 for _ in range(nbuf)]
         for i in range(20):
-            ops.mfma_gemm(x, ws[i % nbuf], epi, sched=3, streamk=sk)
+            ops.mfma_gemm(x, ws[i % nbuf], epi, streamk=sk)
         torch.cuda.synchronize()
         print(json.dumps({"variant": name, "launches": 20}), flush=True)
         del ws

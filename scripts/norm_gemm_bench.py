@@ -55,7 +55,7 @@ def main():
                 R = torch.randn(M, N, device=dev, dtype=bf)
                 ss = torch.zeros(M, 32, device=dev)
                 y = torch.empty(M, N, device=dev, dtype=bf)
-                row["plain_us"] = graph_us(lambda i: ops.mfma_gemm(x, ws[i % nbuf], 0, out=y, sched=3))
+                row["plain_us"] = graph_us(lambda i: ops.mfma_gemm(x, ws[i % nbuf], 0, out=y))
                 row["fused_us"] = graph_us(lambda i: ops.mfma_gemm_norm(x, ws[i % nbuf], kind, ss, 1e-5, out=R))
                 row["blas_us"] = graph_us(lambda i: ops.linear(x, ws[i % nbuf]))
                 # the norm kernel the fusion removes after this projection
@@ -67,7 +67,7 @@ def main():
                 epi = 1 if kind == ops.NORM_SWIGLU else 0
                 No = N // 2 if epi else N
                 y = torch.empty(M, No, device=dev, dtype=bf)
-                row["plain_us"] = graph_us(lambda i: ops.mfma_gemm(x, ws[i % nbuf], epi, out=y, sched=3))
+                row["plain_us"] = graph_us(lambda i: ops.mfma_gemm(x, ws[i % nbuf], epi, out=y))
                 row["fused_us"] = graph_us(lambda i: ops.mfma_gemm_norm(x, ws[i % nbuf], kind, ss, 1e-5, out=y))
                 if not epi:
                     row["blas_us"] = graph_us(lambda i: ops.linear(x, ws[i % nbuf]))

@@ -37,7 +37,7 @@ def main():
             for vname, sk, cus, ph in variants:
                 ops.set_gemm_cus(cus)
                 try:
-                    us = graph_us(lambda i: ops.mfma_gemm(x, ws[i % nbuf], 0, out=y, sched=3, streamk=sk, phases=ph))
+                    us = graph_us(lambda i: ops.mfma_gemm(x, ws[i % nbuf], 0, out=y, streamk=sk, phases=ph))
                 finally:
                     ops.set_gemm_cus(0)
                 print(json.dumps({**base, "variant": vname, "us": round(us, 2), "pf": round(fl / us / 1e9, 3)}),
@@ -46,7 +46,7 @@ def main():
             print(json.dumps({**base, "variant": "hipblaslt", "us": round(us, 2), "pf": round(fl / us / 1e9, 3)}),
                   flush=True)
             # warm weight (one buffer, MALL-resident): the compute-side rate alone
-            us = graph_us(lambda i: ops.mfma_gemm(x, ws[0], 0, out=y, sched=3))
+            us = graph_us(lambda i: ops.mfma_gemm(x, ws[0], 0, out=y))
             print(json.dumps({**base, "variant": "auto_warm", "us": round(us, 2), "pf": round(fl / us / 1e9, 3)}),
                   flush=True)
 

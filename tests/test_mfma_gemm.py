@@ -30,8 +30,10 @@ def test_reference_swiglu_matches_silu_mul_cpu():
 @pytest.mark.parametrize("M,N,K", [(1, 256, 64), (100, 512, 256), (256, 256, 128), (300, 768, 512),
                                    (1000, 1024, 1024), (2048, 2560, 4096), (513, 256, 8192)])
 @pytest.mark.parametrize("epi", [0, 1])
-@pytest.mark.parametrize("sched", [0, 1, 2, 3])
+@pytest.mark.parametrize("sched", [0, 1, 3])
 def test_mfma_gemm_matches_fp32(M, N, K, epi, sched):
+    """Simple kernel (0 compiler order, 1 interleaved) and ping-pong (3); K = 64 and 128 with
+    ``sched=3`` are the automatic fallback to schedule 1 (K no multiple of 128, or below 256)."""
     ops.load_native(required=True)
     x = _rand(M, K, device="cuda", seed=M + K)
     w = _rand(N, K, device="cuda", scale=0.05, seed=N)
@@ -61,7 +63,7 @@ def test_mfma_gemm_half_tile_matches_fp32(M, N, K):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("sched", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("sched", [0, 1, 3, 4])
 def test_mfma_gemm_strided_rows_and_asymmetric_operands(sched):
     """A = row slice of a wider buffer (ldx > K) and an asymmetric W: catches
     row/column swaps in the C write and ldx handling."""

@@ -29,6 +29,9 @@ int dgi_paged_prefill(const void* q, int q_stride, const void* k_cache, const vo
 int dgi_silu_mul(const void* gu, void* out, int T, int I, hipStream_t s);
 int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int M,
                     int N, int K, int nw, hipStream_t s);
+int dgi_skinny_gemm_w8(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
+                       int ldy, int M, int N, int K, int cfg, hipStream_t s);
+int dgi_dequant_fp8(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
 int dgi_mfma_gemm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, int swiglu,
                   int sched, int streamk, int phases, int overlap, hipStream_t s);
 void dgi_set_gemm_cus(int cus);
@@ -221,6 +224,49 @@ void skinny_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w,
   check_rc(dgi_skinny_gemm(x.data_ptr(), (int)x.stride(0), w.data_ptr(), b, out.data_ptr(), (int)out.stride(0),
                            (int)M, (int)N, (int)K, (int)cfg, cur_stream()),
            "skinny_gemm");
+}
+
+// W8A16 decode GEMM: out = (x wq^T) * scale (+ bias); wq [N, K] OCP e4m3, scale [N] fp32 per output channel.
+void skinny_gemm_w8(at::Tensor out, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale,
+                    const c10::optional<at::Tensor>& bias, int64_t cfg) {
+  check_bf16(out, "out"); check_bf16(x, "x"); check_dev(wq, "wq"); check_dev(scale, "scale");
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn, "skinny_gemm_w8: wq must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "skinny_gemm_w8: scale must be float32");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2, "skinny_gemm_w8: 2-D operands");
+  TORCH_CHECK(x.stride(1) == 1 && out.stride(1) == 1 && wq.is_contiguous() && scale.is_contiguous(),
+              "skinny_gemm_w8: row-major operands");
+  TORCH_CHECK(x.device() == wq.device() && x.device() == out.device() && x.device() == scale.device(),
+              "skinny_gemm_w8: operands on one device");
+  const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K && out.size(0) == M && out.size(1) == N && scale.numel() == N,
+              "skinny_gemm_w8: shape mismatch");
+  TORCH_CHECK(M <= 32 && K % 1024 == 0 && N % 16 == 0 && x.stride(0) % 8 == 0,
+              "skinny_gemm_w8: M<=32, K%1024, N%16");
+  const void* b = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N);
+    b = bias->data_ptr();
+  }
+  check_rc(dgi_skinny_gemm_w8(x.data_ptr(), (int)x.stride(0), wq.data_ptr(), scale.data_ptr(), b, out.data_ptr(),
+                              (int)out.stride(0), (int)M, (int)N, (int)K, (int)cfg, cur_stream()),
+           "skinny_gemm_w8");
+}
+
+// out [N, K] bf16 = wq [N, K] e4m3 * scale [N] (the route of every shape skinny_gemm_w8 does not take)
+void dequant_fp8(at::Tensor out, const at::Tensor& wq, const at::Tensor& scale) {
+  check_bf16(out, "out"); check_dev(wq, "wq"); check_dev(scale, "scale");
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn, "dequant_fp8: wq must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "dequant_fp8: scale must be float32");
+  TORCH_CHECK(wq.dim() == 2 && out.dim() == 2 && out.size(0) == wq.size(0) && out.size(1) == wq.size(1),
+              "dequant_fp8: out and wq are [N, K]");
+  TORCH_CHECK(wq.is_contiguous() && out.is_contiguous() && scale.is_contiguous() && scale.numel() == wq.size(0),
+              "dequant_fp8: contiguous operands, one scale per row");
+  TORCH_CHECK(out.device() == wq.device() && out.device() == scale.device(), "dequant_fp8: operands on one device");
+  TORCH_CHECK(wq.size(1) % 16 == 0 && wq.size(0) < (1LL << 31) && wq.size(1) < (1LL << 31), "dequant_fp8: K%16");
+  check_rc(dgi_dequant_fp8(wq.data_ptr(), scale.data_ptr(), out.data_ptr(), (int)wq.size(0), (int)wq.size(1),
+                           cur_stream()),
+           "dequant_fp8");
 }
 
 // LDS-tiled MFMA GEMM (prefill / mixed steps): epi 0 out = x w^T; epi 1 out = SwiGLU with w = [gate; up].
@@ -599,6 +645,8 @@ TORCH_LIBRARY(dgi, m) {
         "Tensor? tree_mask, int tree_n, int tile_rows=128) -> ()");
   m.def("silu_mul(Tensor(a!) out, Tensor gu) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
+  m.def("skinny_gemm_w8(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");
+  m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
   m.def("mfma_gemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, int sched=3, int streamk=0, int phases=0, "
         "bool overlap=True) -> ()");
   m.def("mfma_gemm_norm(Tensor(a!) out, Tensor x, Tensor w, int kind, Tensor(b!) ss, float inv_k, float eps, "
@@ -633,6 +681,8 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("paged_prefill", &paged_prefill);
   m.impl("silu_mul", &silu_mul);
   m.impl("skinny_gemm", &skinny_gemm);
+  m.impl("skinny_gemm_w8", &skinny_gemm_w8);
+  m.impl("dequant_fp8", &dequant_fp8);
   m.impl("mfma_gemm", &mfma_gemm);
   m.impl("mfma_gemm_norm", &mfma_gemm_norm);
   m.impl("mfma_gemm_norm_rope", &mfma_gemm_norm_rope);

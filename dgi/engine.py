@@ -24,6 +24,9 @@ from dgi.sched.scheduler import Scheduler, SchedulerConfig
 from dgi.utils.trace import phase
 
 
+WEIGHT_QUANT_MODES = (None, "fp8")
+
+
 @dataclasses.dataclass
 class EngineConfig:
     model: str = "llama3-8b"
@@ -51,6 +54,12 @@ class EngineConfig:
                                        # stays under this (dgi.sched.slo.StepBudget)
     decode_lookahead: bool = True      # pure-decode graph steps: launch step N+1 before step N's
                                        # tokens are back (``LLMEngine._lookahead``); DGI_DECODE_LOOKAHEAD=0
+    weight_quant: Optional[str] = None   # "fp8": weight-only e4m3 projections (``LlamaModel.quantize_weights``)
+
+    def __post_init__(self):
+        if self.weight_quant not in WEIGHT_QUANT_MODES:
+            raise ValueError(f"EngineConfig.weight_quant={self.weight_quant!r}: supported values are "
+                             f"{', '.join(repr(m) for m in WEIGHT_QUANT_MODES)}")
 
 
 @dataclasses.dataclass
@@ -117,6 +126,9 @@ class LLMEngine:
         t0 = time.perf_counter()
         self.model = model or LlamaModel(self.model_cfg, self.device, cfg.dtype, cfg.layer_start, cfg.layer_end,
                                          seed=cfg.seed, checkpoint=self.checkpoint)
+        if cfg.weight_quant and getattr(self.model, "weight_quant", None) != cfg.weight_quant:
+            # before the KV budget: the pool gets the HBM the bf16 projections give back
+            self.model.quantize_weights(cfg.weight_quant)
         if self.device.type == "cuda":
             torch.cuda.synchronize()
         self.load_seconds = time.perf_counter() - t0
@@ -172,7 +184,8 @@ class LLMEngine:
                       "finished": 0, "step_time": 0.0}
         # MLP row padding measured on this GPU (hipBLASLt kernel-selection cliffs, dgi.runtime.gemm_pad)
         self.mlp_pad_table = None
-        if self.device.type == "cuda" and getattr(self.model, "mlp_pad", None) is None:
+        quantised = getattr(self.model, "weight_quant", None) is not None   # no bf16 weights to time or fold
+        if self.device.type == "cuda" and getattr(self.model, "mlp_pad", None) is None and not quantised:
             from dgi.runtime.gemm_pad import build_for_model
             t1 = time.perf_counter()
             self.mlp_pad_table = build_for_model(self.model, cfg.max_num_batched_tokens)
@@ -187,7 +200,7 @@ class LLMEngine:
         # engine sharing this model (and every captured graph) computes with the same weights — for
         # the models that will run them (dgi.models.llama.NORM_FOLD: routed production shapes by
         # default); other models keep their weights bit for bit
-        if self.device.type == "cuda" and hasattr(self.model, "fold_norms"):
+        if self.device.type == "cuda" and hasattr(self.model, "fold_norms") and not quantised:
             from dgi.models import llama as _llama
             if _llama.NORM_FOLD == "force" or (_llama.NORM_FOLD in ("1", "table") and self.mlp_pad_table is not None):
                 self.model.fold_norms()

@@ -133,6 +133,9 @@ class LlamaLayerWeights:
         self.qkv_bias = qkv_bias   # [qkv_size] for Qwen2, else None (fused into the QKV GEMM epilogue)
 
 
+QUANT_SLOTS = ("qkv", "o", "gate_up", "down")    # the projections quantize_weights replaces
+
+
 def _rand(shape, gen, device, dtype, std):
     t = torch.empty(shape, device=device, dtype=dtype)
     t.normal_(0.0, std, generator=gen)
@@ -179,6 +182,8 @@ class LlamaModel:
         self.norms_folded = False    # fold_norms ran: in_norm / post_norm are ones, qkv / gate_up carry the gains
         self.fold_impl = None        # rows -> run the fused-norm layers? (dgi.runtime.gemm_pad)
         self._ss_buf: Optional[torch.Tensor] = None
+        self.weight_quant: Optional[str] = None     # "fp8": the four projections per layer are ops.Fp8Weight
+        self._quant_scratch: Optional[torch.Tensor] = None
         if checkpoint:
             # real weights: only this rank's layers / TP slices are read (dgi.models.weights)
             from dgi.models.weights import load_checkpoint
@@ -249,6 +254,8 @@ class LlamaModel:
         it.  Idempotent; reloading weights clears the flag."""
         if self.norms_folded:
             return
+        if self.weight_quant:
+            raise RuntimeError("fold_norms: the weights are quantised; fold before quantize_weights")
         with torch.no_grad():
             for L in self.layers:
                 for w, g in ((L.qkv, L.in_norm), (L.gate_up, L.post_norm)):
@@ -265,8 +272,44 @@ class LlamaModel:
                                            dtype=torch.float32)
         self.norms_folded = True
 
+    def quantize_weights(self, mode: str = "fp8") -> "LlamaModel":
+        """Weight-only quantisation of each layer's qkv / o / gate_up / down projection
+        (``ops.quantize_fp8``: e4m3 codes, one fp32 scale per output channel), one layer at a
+        time, dropping the bf16 tensor as it goes.  Norm gains, ``qkv_bias``, ``embed`` and
+        ``lm_head`` keep their dtype.  Steps then run ``_forward_layers_quant``."""
+        if mode != "fp8":
+            raise ValueError(f"quantize_weights: unsupported mode {mode!r} (supported: 'fp8')")
+        if self.weight_quant == mode:
+            return self
+        largest = 0
+        for L in self.layers:
+            for k in QUANT_SLOTS:
+                w = getattr(L, k)
+                if not isinstance(w, ops.Fp8Weight):
+                    setattr(L, k, ops.quantize_fp8(w))
+                    del w
+                largest = max(largest, getattr(L, k).q.numel())
+        # one bf16 buffer the size of the largest projection: the dequantised copy of the steps the
+        # fp8 kernel does not take (allocated here so a graph capture never allocates it)
+        if largest and self.device.type == "cuda":
+            self._quant_scratch = torch.empty(largest, dtype=torch.bfloat16, device=self.device)
+            for L in self.layers:
+                for k in QUANT_SLOTS:
+                    getattr(L, k).scratch = self._quant_scratch
+        self.weight_quant = mode
+        if self.device.type == "cuda":
+            # the KV budget reads driver-free memory: hand the freed bf16 blocks back to the driver
+            torch.cuda.empty_cache()
+        return self
+
+    def _check_not_quantised(self, what: str) -> None:
+        if self.weight_quant:
+            raise RuntimeError(f"{what}: the model's weights are {self.weight_quant}-quantised; "
+                               "load or copy the bf16 weights first, then call quantize_weights")
+
     def load_state_dict_hf(self, sd: dict):
         """Load HF Llama tensor names (``model.layers.N.self_attn.q_proj.weight``...)."""
+        self._check_not_quantised("load_state_dict_hf")
         self.norms_folded = False
         c = self.cfg
         for i, li in enumerate(range(self.layer_start, self.layer_end)):
@@ -295,11 +338,16 @@ class LlamaModel:
         del c
 
     def tensors(self):
-        """(name, tensor) pairs of every weight (lm_head omitted when tied)."""
+        """(name, tensor) pairs of every weight (lm_head omitted when tied).  A quantised
+        projection yields its codes and its scales as ``<name>.q`` and ``<name>.scale``."""
         for i, L in enumerate(self.layers):
             for k in LlamaLayerWeights.__slots__:
-                if getattr(L, k) is not None:
-                    yield f"layers.{self.layer_start + i}.{k}", getattr(L, k)
+                t = getattr(L, k)
+                if isinstance(t, ops.Fp8Weight):
+                    yield f"layers.{self.layer_start + i}.{k}.q", t.q
+                    yield f"layers.{self.layer_start + i}.{k}.scale", t.scale
+                elif t is not None:
+                    yield f"layers.{self.layer_start + i}.{k}", t
         for k in ("embed", "norm"):
             t = getattr(self, k)
             if t is not None:
@@ -310,6 +358,9 @@ class LlamaModel:
     def copy_from(self, other: "LlamaModel") -> "LlamaModel":
         """Copy weights of the overlapping layer range from another instance
         (any device) — used to compare CPU / GPU / sharded models exactly."""
+        if self.weight_quant != other.weight_quant:
+            raise RuntimeError(f"copy_from: this model's weights are {self.weight_quant or 'unquantised'}, the "
+                               f"source's {other.weight_quant or 'unquantised'}; copy first, then quantize_weights")
         src = dict(other.tensors())
         self.norms_folded = other.norms_folded
         for name, t in self.tensors():
@@ -321,7 +372,9 @@ class LlamaModel:
         n = 0
         for L in self.layers:
             for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias):
-                if t is not None:
+                if isinstance(t, ops.Fp8Weight):
+                    n += t.nbytes()      # 1 byte per element + one fp32 scale per row
+                elif t is not None:
                     n += t.numel() * t.element_size()
         for t in (self.embed, self.norm):
             if t is not None:
@@ -633,6 +686,36 @@ class LlamaModel:
         out_r.record_stream(main)
         return out_h, out_r
 
+    def _forward_layers_quant(self, h: torch.Tensor, meta: AttnMeta, residual: Optional[torch.Tensor] = None,
+                              trim_last: Optional[torch.Tensor] = None):
+        """The layers of a weight-quantised model: norm -> linear -> attention -> linear -> norm ->
+        SwiGLU(linear) -> linear, every projection through ``ops.linear`` (the W8A16 kernel for
+        decode-sized steps, dequantise + bf16 GEMM otherwise).  No fused-norm, fused-decode, TBO or
+        MFMA-table layers: those read bf16 weights."""
+        eps = self.cfg.rms_eps
+        for i, L in enumerate(self.layers):
+            if residual is None:
+                residual = h
+                h = ops.rmsnorm(h, L.in_norm, eps)
+            else:
+                ops.fused_add_rmsnorm(h, residual, L.in_norm, eps)
+            attn = self.attention(i, ops.linear(h, L.qkv, L.qkv_bias), meta)
+            if trim_last is not None and i == len(self.layers) - 1:
+                attn = attn.index_select(0, trim_last)
+                residual = residual.index_select(0, trim_last)
+            h = ops.linear(attn, L.o)
+            if self.reduce is not None:
+                self.reduce(h)
+            ops.fused_add_rmsnorm(h, residual, L.post_norm, eps)
+            h = ops.linear(ops.silu_mul(ops.linear(h, L.gate_up)), L.down)
+            if self.reduce is not None:
+                self.reduce(h)
+            if self.capture_layers and (self.layer_start + i) in self.capture_layers:
+                self.captured[self.layer_start + i] = h + residual
+            if self.layer_hook is not None:
+                self.layer_hook(self.layer_start + i)
+        return h, residual
+
     def forward_layers(self, h: torch.Tensor, meta: AttnMeta, residual: Optional[torch.Tensor] = None,
                        trim_last: Optional[torch.Tensor] = None):
         """Run the local layers.  ``trim_last`` (row indices): the last layer's
@@ -642,6 +725,8 @@ class LlamaModel:
         c = self.cfg
         eps = c.rms_eps
         T = h.shape[0]
+        if self.weight_quant:
+            return self._forward_layers_quant(h, meta, residual, trim_last)
         if self.layers:
             split = self._tbo_ok(h, meta, trim_last)
             if split is not None:

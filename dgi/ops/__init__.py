@@ -19,6 +19,8 @@ from typing import Optional
 import numpy as np
 import torch
 
+from dgi.ops.fp8 import Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
+
 _LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_C.so")
 _loaded = False
 _load_error: Optional[str] = None
@@ -403,9 +405,87 @@ def _skinny_cfg(M: int, N: int) -> int:
     return 5 if (M > 8 and N >= 16384) else 0
 
 
-def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+# FP8 weight-only projections (skinny_gemm_fp8.hip).  The W8A16 kernel takes every decode-sized
+# step it can launch: M <= 32, K % 1024 == 0, N % 16 == 0 — without the bf16 kernel's K <= 4096
+# rule, which only marks where hipBLASLt wins and hipBLASLt cannot read this format.  Everything
+# else is dequantised to bf16 (dequant_fp8) and runs the bf16 GEMM.
+# launch configs of skinny_gemm_w8: cfg -> (waves per workgroup, column tiles per wave, 128-deep
+# K steps per load group, ring depth); a config needs N % (16 * tiles) == 0 and
+# (K / 128) % (waves * steps) == 0
+SKINNY_W8_CFGS = {1: (8, 1, 1, 4), 2: (8, 1, 1, 2), 3: (4, 1, 2, 2), 4: (4, 1, 2, 4), 5: (8, 2, 1, 2),
+                  6: (4, 1, 1, 8), 7: (16, 1, 1, 2), 8: (8, 4, 1, 2)}
+SKINNY_W8_CFG = int(os.environ.get("DGI_SKINNY_W8_CFG", "0"))    # > 0 forces a launch config (sweeps)
+
+
+def skinny_w8_cfg_ok(cfg: int, N: int, K: int) -> bool:
+    """Whether launch config ``cfg`` of ``skinny_gemm_w8`` divides an [N, K] weight."""
+    nw, nt, u, _d = SKINNY_W8_CFGS[cfg or 2]
+    return K % 1024 == 0 and N % (16 * nt) == 0 and (K // 128) % (nw * u) == 0
+
+
+def _skinny_w8_cfg(M: int, N: int) -> int:
+    """Launch config per row count and width (profiles/fp8_weights/README.md, weights cold, hipGraph-timed):
+    every lane reads its X fragment from L2 whatever M is, so from a few rows on the kernel is bound by
+    that traffic and wider column tiles (one X fragment for 2 or 4 weight tiles) win wherever enough
+    workgroups remain: N >= 6144 for two tiles, the gate_up widths at M > 8 for four.  Between one and
+    two workgroups of two tiles per CU (70B qkv: 320 on 256 CUs) the second round runs a quarter full:
+    one tile up to 8 rows, four above."""
+    if SKINNY_W8_CFG > 0:
+        return SKINNY_W8_CFG
+    if M <= 2 or N < 6144 or N % 64:
+        return 0
+    if 256 < N // 32 < 512:
+        return 8 if M > 8 else 0
+    return 8 if (M > 8 and N >= 16384) else 5
+
+
+def _use_skinny_w8(M: int, N: int, K: int) -> bool:
+    return 0 < M <= min(32, SKINNY_MAX_M) and K % 1024 == 0 and N % 16 == 0
+
+
+def linear_fp8_ref(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return torch.nn.functional.linear(x.float(), w.q.float() * w.scale[:, None],
+                                      None if bias is None else bias.float()).to(x.dtype)
+
+
+def dequant_fp8(w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] copy of an fp8 weight; ``out``: a flat bf16 buffer of >= N*K elements."""
+    N, K = w.shape
+    if out is None or out.numel() < N * K or out.device != w.device or out.dtype != torch.bfloat16:
+        out = torch.empty(N * K, dtype=torch.bfloat16, device=w.device)
+    out = out.view(-1)[: N * K].view(N, K)
+    if w.q.is_cuda:
+        load_native(required=True)
+        _call("dequant_fp8", out, w.q, w.scale)     # K % 16 == 0, checked by the op
+    else:
+        out.copy_(w.dequant(torch.bfloat16))
+    return out
+
+
+def _linear_fp8(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor], out: Optional[torch.Tensor]):
+    if x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16:
+        M, K = x.shape
+        N = w.shape[0]
+        if _use_skinny_w8(M, N, K) and x.stride(1) == 1 and x.stride(0) % 8 == 0:
+            load_native(required=True)
+            if out is None:
+                out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+            _call("skinny_gemm_w8", out, x, w.q, w.scale, bias, _skinny_w8_cfg(M, N))
+            return out
+        r = torch.nn.functional.linear(x, dequant_fp8(w, w.scratch), bias)
+    else:
+        r = linear_fp8_ref(x, w, bias)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def linear(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = x @ w.T (+ bias) for a 2-D activation; [N, K] weights as stored."""
+    """y = x @ w.T (+ bias) for a 2-D activation; [N, K] weights as stored (bf16 tensor or ``Fp8Weight``)."""
+    if isinstance(w, Fp8Weight):
+        return _linear_fp8(x, w, bias, out)
     if x.dim() != 2:
         return torch.nn.functional.linear(x, w, bias)
     M, K = x.shape

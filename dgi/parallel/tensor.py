@@ -108,6 +108,8 @@ class TPEngine(LLMEngine):
             dev = torch.device("cuda", torch.cuda.current_device())
         model = TPLlamaModel(full, dev, cfg.dtype, tp_rank, tp, group, seed=cfg.seed, checkpoint=ckpt)
         cfg = dataclasses.replace(cfg, device=str(dev))
+        if cfg.weight_quant:        # before the page budget, like LLMEngine
+            model.quantize_weights(cfg.weight_quant)
         if tp > 1:
             # every rank must hold the same page count (block ids are shared): agree on the minimum
             nb = engine_block_budget(cfg, model.cfg, model.num_local_layers, dev)

@@ -100,7 +100,8 @@ class Router:
         dev = str(fabric.device) if fabric is not None else ("cuda" if torch.cuda.is_available() else "cpu")
         cfg = EngineConfig(model=args.model, device=dev, max_num_seqs=args.max_num_seqs,
                            max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
-                           use_graphs=dev.startswith("cuda") and not args.no_graphs, seed=args.seed)
+                           use_graphs=dev.startswith("cuda") and not args.no_graphs, seed=args.seed,
+                       weight_quant=args.weight_quant)
         self.drv = None
         self.chans = {}
         self.load = collections.Counter()
@@ -335,7 +336,8 @@ def _prefill_loop(args, fabric, layout) -> None:
     cap = args.prefill_local_cap if args.prefill_local_cap >= 0 else prefill_overflow_cap(layout)
     cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=64 + cap,
                        max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
-                       use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed)
+                       use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed,
+                       weight_quant=args.weight_quant)
     srv = PrefillServer(cfg, fabric, layout, local_cap=cap, report_tokens=True)
     inbox = CtrlChannel(fabric, layout.drivers[0], 1, tag="req")
     stopping = False
@@ -365,7 +367,8 @@ def _replica_loop(args, fabric, layout) -> None:
     from dgi.parallel.pd import DecodeDriver
     cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=args.max_num_seqs,
                        max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
-                       use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed)
+                       use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed,
+                       weight_quant=args.weight_quant)
     drv = DecodeDriver(cfg, fabric, layout)
     drv.track_arrivals = True
     drv.forward_tokens = True
@@ -397,6 +400,8 @@ def main(argv=None) -> int:
     ap.add_argument("--max-model-len", type=int, default=4096)
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--weight-quant", default=None, choices=["fp8"],
+                    help="weight-only quantisation of the layer projections (default: bf16 weights)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     fabric = layout = None
@@ -423,7 +428,7 @@ def main(argv=None) -> int:
             cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=args.max_num_seqs,
                                max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                                use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs,
-                               seed=args.seed, enable_prefix_caching=False)
+                               seed=args.seed, enable_prefix_caching=False, weight_quant=args.weight_quant)
             w = StageWorker(cfg, fabric, layout.group_of(fabric.rank), kv_sources=layout.prefill_ranks)
             while w.run() != "stop":
                 pass

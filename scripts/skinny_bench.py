@@ -4,7 +4,9 @@
 Weights rotate over enough copies (> 1 GiB) that every call streams from HBM,
 as in a real decode step where a layer's weights were last touched one full
 model pass ago (the 256 MB MALL cannot hold them).  Prints one JSON line per
-(shape, M, impl) with the time and the achieved weight bandwidth.
+(shape, M, impl) with the time and the achieved weight bandwidth.  ``--fp8-cfg``
+adds the W8A16 kernel (``skinny_gemm_w8``, e4m3 weights at half the bytes) as
+``fp8_c<cfg>`` columns, over the same number of rotating copies.
 """
 import argparse
 import json
@@ -24,10 +26,29 @@ SHAPES = {  # name: (N, K)
 }
 
 
-def timed(fn, iters):
+def timed(fn, iters, graph=False, reps=5):
     for _ in range(3):
         fn(0)
     torch.cuda.synchronize()
+    if graph:
+        # one captured graph of ``iters`` launches over the rotating copies, replayed ``reps`` times:
+        # kernel time without the host's launch gaps (short kernels are launch-bound eagerly)
+        g = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                for i in range(iters):
+                    fn(i)
+        g.replay()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / (iters * reps) * 1000.0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for i in range(iters):
@@ -43,6 +64,9 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES))
     ap.add_argument("--cfg", type=int, nargs="+", default=[0])
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--fp8-cfg", type=int, nargs="*", default=[0], help="skinny_gemm_w8 launch configs (none: skip)")
+    ap.add_argument("--no-hipblaslt", action="store_true")
+    ap.add_argument("--graph", action="store_true", help="time hipGraph replays instead of eager launches")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ops.load_native(required=True)
@@ -51,22 +75,33 @@ def main():
         N, K = SHAPES[name]
         copies = max(2, -(-(1 << 30) // (N * K * 2)))
         ws = [torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02 for _ in range(copies)]
+        qs = [ops.quantize_fp8(w) for w in ws] if a.fp8_cfg else []
         for M in a.ms:
             x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
             out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-            impls = {"hipblaslt": lambda i: F.linear(x, ws[i % copies])}
+            impls = {} if a.no_hipblaslt else {"hipblaslt": lambda i: F.linear(x, ws[i % copies])}
             for c in a.cfg:
                 impls[f"skinny_c{c}"] = (lambda c_: lambda i: torch.ops.dgi.skinny_gemm(
                     out, x, ws[i % copies], None, c_))(c)
+            for c in a.fp8_cfg:
+                if ops.skinny_w8_cfg_ok(c, N, K):
+                    impls[f"fp8_c{c}"] = (lambda c_: lambda i: torch.ops.dgi.skinny_gemm_w8(
+                        out, x, qs[i % copies].q, qs[i % copies].scale, None, c_))(c)
             ref = F.linear(x.float(), ws[0].float())
             torch.ops.dgi.skinny_gemm(out, x, ws[0], None, 0)
             err = (out.float() - ref).abs().max().item()
+            err8 = None
+            if a.fp8_cfg:
+                torch.ops.dgi.skinny_gemm_w8(out, x, qs[0].q, qs[0].scale, None, 0)
+                err8 = (out.float() - F.linear(x.float(), qs[0].dequant())).abs().max().item()
             for impl, fn in impls.items():
-                us = timed(fn, a.iters)
+                us = timed(fn, a.iters, a.graph)
+                fp8 = impl.startswith("fp8")
                 rows.append({"shape": name, "M": M, "N": N, "K": K, "impl": impl, "us": round(us, 2),
-                             "weight_TBs": round(N * K * 2 / us / 1e6, 2), "max_err": round(err, 4)})
+                             "weight_TBs": round(N * K * (1 if fp8 else 2) / us / 1e6, 2),
+                             "max_err": round(err8 if fp8 else err, 4), "timing": "graph" if a.graph else "eager"})
                 print(json.dumps(rows[-1]), flush=True)
-        del ws
+        del ws, qs
         torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "w") as f:

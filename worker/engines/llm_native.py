@@ -14,7 +14,8 @@ Config keys accepted (SURVEY Appendix C mapping): ``model_id``, ``device``,
 ``mem_fraction_static``/``gpu_memory_utilization`` -> KV fraction,
 ``max_running_requests``/``max_num_seqs``, ``chunked_prefill_size``,
 ``enable_prefix_caching``, ``context_length``/``max_model_len``,
-``num_blocks``, ``use_graphs``/``enforce_eager``; nested ``sglang``/``vllm``/
+``num_blocks``, ``use_graphs``/``enforce_eager``, ``quantization``/``weight_quant``
+(``"fp8"``: weight-only e4m3 projections; anything else is served unquantised); nested ``sglang``/``vllm``/
 ``native`` dicts are merged in.
 """
 from __future__ import annotations
@@ -96,6 +97,13 @@ class NativeLLMEngine(LLMBaseEngine):
             logger.warning("serving RANDOM-INIT weights for %s (allow_random_weights)", model_id)
         self.weights = ckpt or "random-init"
         mc = get_config(ckpt or model_id)
+        quant = c.get("weight_quant", c.get("quantization"))
+        if quant is not None and str(quant).lower() in ("", "none"):
+            quant = None
+        if quant is not None and str(quant).lower() != "fp8":
+            logger.warning("quantization=%r is not supported by the native engine (supported: 'fp8', weight-only); "
+                           "serving %s unquantised", quant, model_id)
+            quant = None
         frac = c.get("mem_fraction_static", c.get("gpu_memory_utilization", c.get("kv_fraction", 0.9)))
         ecfg = EngineConfig(
             model=model_id, device=device, model_path=ckpt,
@@ -106,7 +114,7 @@ class NativeLLMEngine(LLMBaseEngine):
             enable_prefix_caching=bool(c.get("enable_prefix_caching", True)),
             use_graphs=bool(c.get("use_graphs", not c.get("enforce_eager", False))) and device != "cpu",
             seed=int(c.get("seed", 0)), block_size=int(c.get("block_size", 16)),
-            host_kv_gb=float(c.get("host_kv_gb", 0.0)),
+            host_kv_gb=float(c.get("host_kv_gb", 0.0)), weight_quant="fp8" if quant is not None else None,
             graph_buckets=tuple(c["graph_batch_buckets"]) if c.get("graph_batch_buckets") else None)
         spec = c.get("speculative")
         if spec:

@@ -34,7 +34,6 @@ int dgi_skinny_gemm_w8(const void* x, int ldx, const void* w, const void* scale,
 int dgi_dequant_fp8(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
 int dgi_mfma_gemm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, int swiglu,
                   int sched, int streamk, int phases, int overlap, hipStream_t s);
-void dgi_set_gemm_cus(int cus);
 int dgi_gemm_split_timeouts(int reset);
 int dgi_mfma_gemm_norm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, int kind,
                        float* ss, int ss_ld, float inv_k, float eps, int phases, hipStream_t s);
@@ -271,7 +270,7 @@ void dequant_fp8(at::Tensor out, const at::Tensor& wq, const at::Tensor& scale) 
 
 // LDS-tiled MFMA GEMM (prefill / mixed steps): epi 0 out = x w^T; epi 1 out = SwiGLU with w = [gate; up].
 // sched 3: the ping-pong kernel, steered by streamk (split-K policy: 0 auto, 1 off, 2 whenever), phases per
-// K tile (0 auto, 2, 4) and overlap; 0 / 1: the one-barrier-per-K-step kernel; 4: the half tile (epi 0).
+// K tile (0 auto, 2, 4) and overlap; 0 / 1: the one-barrier-per-K-step kernel.
 void mfma_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, int64_t epi, int64_t sched,
                int64_t streamk, int64_t phases, bool overlap) {
   check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
@@ -282,8 +281,7 @@ void mfma_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, int64_t
   TORCH_CHECK(w.size(1) == K && out.size(0) == M, "mfma_gemm: shape mismatch");
   TORCH_CHECK((epi == 0 || epi == 1) && streamk >= 0 && streamk <= 2 && (phases == 0 || phases == 2 || phases == 4),
               "mfma_gemm: epi 0 (store) or 1 (SwiGLU), streamk 0-2, phases 0, 2 or 4");
-  TORCH_CHECK(sched == 0 || sched == 1 || sched == 3 || sched == 4, "mfma_gemm: schedule 0, 1, 3 or 4");
-  TORCH_CHECK(sched != 4 || epi == 0, "mfma_gemm: schedule 4 (half tile) is a plain GEMM");
+  TORCH_CHECK(sched == 0 || sched == 1 || sched == 3, "mfma_gemm: schedule 0, 1 or 3");
   TORCH_CHECK(out.size(1) == (epi == 1 ? N / 2 : N), "mfma_gemm: output columns");
   TORCH_CHECK(N % 256 == 0 && K % 64 == 0 && x.stride(0) % 8 == 0 && out.stride(0) % 4 == 0,
               "mfma_gemm: N%256, K%64, ldx%8, ldy%4");
@@ -623,15 +621,11 @@ void tree_verify(at::Tensor accept_len, at::Tensor path, at::Tensor out_tokens,
                            cur_stream()), "tree_verify");
 }
 
-// CUs the MFMA GEMM's persistent launches size their grid for (0 = the device's; a CU-masked
-// two-batch-overlap step sets the GEMM stream's share)
-void set_gemm_cus(int64_t cus) { dgi_set_gemm_cus(static_cast<int>(cus)); }
 int64_t gemm_split_timeouts(bool reset) { return dgi_gemm_split_timeouts(reset ? 1 : 0); }
 
 }  // namespace
 
 TORCH_LIBRARY(dgi, m) {
-  m.def("set_gemm_cus(int cus) -> ()", &set_gemm_cus);
   m.def("gemm_split_timeouts(bool reset) -> int", &gemm_split_timeouts);
   m.def("rmsnorm(Tensor(a!) out, Tensor x, Tensor w, float eps) -> ()");
   m.def("fused_add_rmsnorm(Tensor(a!) x, Tensor(b!) residual, Tensor w, float eps) -> ()");

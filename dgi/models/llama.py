@@ -35,31 +35,13 @@ from dgi.runtime.batch import AttnMeta
 
 # DGI_TRIM_LAST_LAYER=0 runs the last layer's o-proj and MLP on every row (A/B switch)
 TRIM_LAST_LAYER = os.environ.get("DGI_TRIM_LAST_LAYER", "1") != "0"
-# DGI_QKV_PAD=1: the QKV GEMM reuses the MLP's padded rows; DGI_OPROJ_PAD=1: the o-proj
-# runs on a zero-padded attention output.  Both off by default: with them the start-up
-# table times qkv / o-proj at every row count too, and the 70B bench measured no gain
-# (1755 / 1743 vs 1761 / 1750 tok/s, profiles/r2_bench70b_qkvpad_ab.md)
-QKV_PAD = os.environ.get("DGI_QKV_PAD", "0") == "1"
-OPROJ_PAD = os.environ.get("DGI_OPROJ_PAD", "0") == "1"
 # mixed steps: decode-row attention on a side stream beside the prefill-row attention
 ATTN_OVERLAP = os.environ.get("DGI_ATTN_OVERLAP", "1") == "1"
-# Two-batch overlap (TBO) of large pure-decode steps (``LlamaModel._forward_layers_tbo``): the
-# rows are cut in two tile-aligned halves whose decode attention runs on a few CUs of every
-# XCD (``DGI_TBO_SIDE`` per XCD) while the other half's GEMM chain runs on the rest.  Two
-# plain streams do not overlap (a full-chip GEMM holds every CU: graph-forked GEMM + HBM stream
-# 0.713 vs 0.751 ms serial); CU-masked streams do for a plain HBM stream (1.56 vs 1.70 ms
-# eagerly), and a captured graph drops the masks, so TBO steps run eagerly.  OFF by default:
-# on the 27-layer 70B decode stage at 768 rows it MEASURED 67.0 ms against 41.9 eager / 39.8
-# graph-replayed (profiles/r5_pd/README.md) — split-KV decode attention is latency-bound per
-# CU (32 CUs ran it 3.1x slower than 256, not 8x) and the half-size GEMMs beside it ran 1.85x
-# slower than their share; DGI_TBO=1 turns it on for experiments.
-TBO = os.environ.get("DGI_TBO", "0") == "1"
 # steps of <= 16 rows that carry prefill tokens (an EAGLE tree verify: N tree nodes per sequence
 # under a tree mask) take the fused decode layers too — the qkv / gate_up kernels are per-row
 # (norm prologue, RoPE + paged-KV epilogue at each row's own position / slot) and the attention
 # dispatch already splits decode and prefill rows; 5 kernels per layer instead of 9
 FUSED_SMALL_PREFILL = os.environ.get("DGI_FUSED_SMALL_PREFILL", "1") == "1"
-TBO_MIN_ROWS = int(os.environ.get("DGI_TBO_MIN_ROWS", "512"))
 # Fused-norm layers (``LlamaModel._forward_layers_folded``): the RMSNorm gains are folded into the
 # qkv / gate_up weights once (``fold_norms``), the o-proj and down GEMMs add into the residual
 # stream in their epilogue and emit its per-row sums of squares, and the qkv / gate_up GEMMs
@@ -78,32 +60,7 @@ NORM_FOLD_MIN_ROWS = int(os.environ.get("DGI_NORM_FOLD_MIN_ROWS", "256"))
 # fused-norm layers: RoPE + the paged-KV write in the qkv GEMM's epilogue (EPI 5) where the geometry
 # allows (NeoX rotary over 128-dim heads, q / kv column blocks of 256); "0" keeps rope_cache
 NORM_FOLD_ROPE = os.environ.get("DGI_NORM_FOLD_ROPE", "1") != "0"
-TBO_SIDE_PER_XCD = int(os.environ.get("DGI_TBO_SIDE", "4"))
 
-
-def tbo_split(T: int) -> Optional[tuple]:
-    """(rows of half A, rows of half B) of a T-row TBO step: B is half of T rounded down to the
-    256-row GEMM tile (at least one tile), A the rest; None below ``TBO_MIN_ROWS``."""
-    if T < max(512, TBO_MIN_ROWS):
-        return None
-    b = max(256, (T // 2) // 256 * 256)
-    return T - b, b
-
-
-class TboStreams:
-    """The CU-masked stream pair of a device's TBO steps (created once per process)."""
-
-    def __init__(self, device: torch.device, side_per_xcd: int):
-        from dgi.utils.streams import cu_masked_stream, xcd_split
-        n = torch.cuda.get_device_properties(device).multi_processor_count
-        main, side = xcd_split(n, side_per_xcd)
-        self.gemm = cu_masked_stream("tbo_gemm", device, main)
-        self.attn = cu_masked_stream("tbo_attn", device, side)
-        self.gemm_cus = len(main)
-        self.events = [torch.cuda.Event() for _ in range(4)]     # q ready / attention done, per half
-
-
-_TBO_STREAMS: dict = {}
 
 def fold_decision(mode: str, rows: int, fold_impl) -> bool:
     """Whether a GPU step of ``rows`` rows runs the fused-norm layers under ``DGI_NORM_FOLD`` =
@@ -177,7 +134,6 @@ class LlamaModel:
         # (P/D layer-streamed migration sends finished layers while later ones compute)
         self.layer_hook = None
         self._pad_buf: Optional[torch.Tensor] = None
-        self._attn_buf: Optional[torch.Tensor] = None
         self.load_info: Optional[dict] = None
         self.norms_folded = False    # fold_norms ran: in_norm / post_norm are ones, qkv / gate_up carry the gains
         self.fold_impl = None        # rows -> run the fused-norm layers? (dgi.runtime.gemm_pad)
@@ -421,7 +377,8 @@ class LlamaModel:
         return out
 
     def _mlp_rows(self, T: int, like: torch.Tensor) -> int:
-        """Padded MLP row count for a T-row step, and the o-proj buffer it needs."""
+        """Padded MLP row count for a T-row step; sizes the buffer the o-proj writes into and
+        zeroes its pad rows."""
         if self.mlp_pad is None or not like.is_cuda or torch.cuda.is_current_stream_capturing():
             return T
         Mp = self.mlp_pad(T)
@@ -431,13 +388,44 @@ class LlamaModel:
         if buf is None or buf.shape[0] < Mp or buf.dtype != like.dtype or buf.device != like.device:
             buf = self._pad_buf = torch.empty(max(Mp, 4096), like.shape[1], dtype=like.dtype, device=like.device)
         buf[T:Mp].zero_()       # pad rows: zeros in, ignored out
-        if OPROJ_PAD:           # attention output rows past T stay zero for the padded o-proj
-            ab = self._attn_buf
-            q = self.cfg.q_size
-            if ab is None or ab.shape[0] < Mp or ab.dtype != like.dtype or ab.device != like.device:
-                ab = self._attn_buf = torch.empty(max(Mp, 4096), q, dtype=like.dtype, device=like.device)
-            ab[T:Mp].zero_()
         return Mp
+
+    # ------------------------------------------------------------------ pieces the layer loops share
+    def _first_norm(self, h: torch.Tensor, residual: Optional[torch.Tensor], L: LlamaLayerWeights) -> tuple:
+        """A layer's input norm: (normalised h, residual stream).  Without a residual (the first
+        local layer) h becomes the stream and the norm writes a fresh tensor; otherwise h is
+        added into the stream and normalised in place."""
+        if residual is None:
+            return ops.rmsnorm(h, L.in_norm, self.cfg.rms_eps), h
+        ops.fused_add_rmsnorm(h, residual, L.in_norm, self.cfg.rms_eps)
+        return h, residual
+
+    def _trimmed_tail(self, i: int, L: LlamaLayerWeights, attn: torch.Tensor, stream: torch.Tensor,
+                      rows: torch.Tensor) -> tuple:
+        """The last layer after its attention (which has written every row's K/V), on the logits
+        rows ``rows`` alone: o-proj, add + norm, MLP.  Returns (MLP output, stream) of those rows;
+        nothing is recorded in ``captured`` (forward() never trims while layers are captured)."""
+        eps = self.cfg.rms_eps
+        attn = attn.index_select(0, rows)
+        stream = stream.index_select(0, rows)
+        h = ops.linear(attn, L.o)
+        if self.reduce is not None:
+            self.reduce(h)
+        ops.fused_add_rmsnorm(h, stream, L.post_norm, eps)
+        h = ops.linear(ops.silu_mul(ops.linear(h, L.gate_up)), L.down)
+        if self.reduce is not None:
+            self.reduce(h)
+        if self.layer_hook is not None:
+            self.layer_hook(self.layer_start + i)
+        return h, stream
+
+    def _end_layer(self, i: int, h: torch.Tensor, residual: torch.Tensor) -> None:
+        """EAGLE-3 feature tap and the layer hook of local layer ``i``."""
+        li = self.layer_start + i
+        if self.capture_layers and li in self.capture_layers:
+            self.captured[li] = h + residual
+        if self.layer_hook is not None:
+            self.layer_hook(li)
 
     def _fused_decode(self, h: torch.Tensor, meta: AttnMeta) -> tuple:
         """(fuse qkv, fuse gate_up) for this step; (False, False) = unfused layers."""
@@ -479,11 +467,7 @@ class LlamaModel:
                 residual = new_res
                 attn = self.attention(i, qkv, meta, rope=not rope_epi)
             else:
-                if residual is None:
-                    residual = h
-                    h = ops.rmsnorm(h, L.in_norm, eps)
-                else:
-                    ops.fused_add_rmsnorm(h, residual, L.in_norm, eps)
+                h, residual = self._first_norm(h, residual, L)
                 attn = self.attention(i, ops.linear(h, L.qkv, L.qkv_bias), meta)
             h = ops.decode_proj(attn, L.o)
             if self.reduce is not None:
@@ -499,10 +483,7 @@ class LlamaModel:
             h = ops.linear(act, L.down)
             if self.reduce is not None:
                 self.reduce(h)
-            if self.capture_layers and (self.layer_start + i) in self.capture_layers:
-                self.captured[self.layer_start + i] = h + residual
-            if self.layer_hook is not None:
-                self.layer_hook(self.layer_start + i)
+            self._end_layer(i, h, residual)
         return h, residual
 
     # ------------------------------------------------------------------ fused-norm layers
@@ -572,14 +553,7 @@ class LlamaModel:
                 qkv = ops.mfma_gemm_norm(R, L.qkv, ops.NORM_PLAIN, ss, eps)
                 attn = self.attention(i, qkv, meta)
             if trim_last is not None and i == n - 1:
-                attn = attn.index_select(0, trim_last)
-                Rs = R.index_select(0, trim_last)
-                ho = ops.linear(attn, L.o)
-                ops.fused_add_rmsnorm(ho, Rs, L.post_norm, eps)
-                out = ops.linear(ops.silu_mul(ops.linear(ho, L.gate_up)), L.down)
-                if self.layer_hook is not None:
-                    self.layer_hook(self.layer_start + i)
-                return out, Rs
+                return self._trimmed_tail(i, L, attn, R, trim_last)      # reduce is None here (_fold_ok)
             ops.mfma_gemm_norm(attn, L.o, ops.NORM_RES, ss, eps, out=R)
             act = ops.mfma_gemm_norm(R, L.gate_up, ops.NORM_SWIGLU, ss, eps)
             ops.mfma_gemm_norm(act, L.down, ops.NORM_RES, ss, eps, out=R)
@@ -589,132 +563,13 @@ class LlamaModel:
                 self.layer_hook(self.layer_start + i)
         return R, None
 
-    # ------------------------------------------------------------------ two-batch overlap
-    def _tbo_ok(self, h: torch.Tensor, meta: AttnMeta, trim_last) -> Optional[tuple]:
-        if not (TBO and h.is_cuda and self.layers and meta.num_prefill_tokens == 0 and trim_last is None
-                and self.reduce is None and not self.capture_layers and self.layer_hook is None
-                and h.dtype == torch.bfloat16 and not torch.cuda.is_current_stream_capturing()):
-            return None
-        return tbo_split(h.shape[0])
-
-    @staticmethod
-    def _rows_meta(meta: AttnMeta, a: int, b: int) -> AttnMeta:
-        """Decode metadata of rows [a, b) of a pure-decode step."""
-        return AttnMeta(positions=meta.positions[a:b], slot_mapping=meta.slot_mapping[a:b], num_decode=b - a,
-                        dec_block_tables=meta.dec_block_tables[a:b], dec_context_lens=meta.dec_context_lens[a:b],
-                        dec_max_splits=meta.dec_max_splits, dec_part_size=meta.dec_part_size,
-                        dec_workspace=meta.dec_workspace, num_prefill_tokens=0, logits_indices=None)
-
-    def _forward_layers_tbo(self, h: torch.Tensor, meta: AttnMeta, residual: Optional[torch.Tensor], split: tuple):
-        """Pure-decode layers as two halves A | B: half X's attention (RoPE + paged KV write +
-        split-KV decode attention) runs on the side stream's CUs while the GEMM stream runs
-        the other half's o-proj, MLP and next QKV, so the attention (~23 % of a 768-row 70B
-        stage step) hides under GEMMs instead of following them.  Per layer, in issue order::
-
-            gemm: pre(A, i+1) | post(B, i) pre(B, i+1) | post(A, i+1) ...
-            attn:        attn(A, i+1) ->         attn(B, i+1) -> ...
-
-        pre = (add +) RMSNorm + QKV GEMM; post = o-proj + add + RMSNorm + gate_up (SwiGLU) + down.
-        Row-independent, so the outputs equal the one-batch step's up to GEMM blocking."""
-        dev = h.device
-        st = _TBO_STREAMS.get(dev.index)
-        if st is None:
-            st = _TBO_STREAMS[dev.index] = TboStreams(dev, TBO_SIDE_PER_XCD)
-        G, S = st.gemm, st.attn
-        eq = st.events[:2]
-        ea = st.events[2:]
-        c = self.cfg
-        eps = c.rms_eps
-        T = h.shape[0]
-        na = split[0]
-        bounds = ((0, na), (na, T))
-        metas = [self._rows_meta(meta, a, b) for a, b in bounds]
-        main = torch.cuda.current_stream()
-        G.wait_stream(main)
-        S.wait_stream(main)
-        hs = [h[a:b] for a, b in bounds]
-        res = [None if residual is None else residual[a:b] for a, b in bounds]
-        rows = [b - a for a, b in bounds]
-        impl = [(self.mlp_impl(r) if self.mlp_impl is not None else (False, False)) +
-                (self.proj_impl(r) if self.proj_impl is not None else (False, False)) for r in rows]
-        qkv = [None, None]
-        att = [None, None]
-        n = len(self.layers)
-        ops.set_gemm_cus(st.gemm_cus)
-        try:
-            def pre(x, i):
-                L = self.layers[i]
-                if res[x] is None:
-                    res[x] = hs[x]
-                    hs[x] = ops.rmsnorm(hs[x], L.in_norm, eps)
-                else:
-                    ops.fused_add_rmsnorm(hs[x], res[x], L.in_norm, eps)
-                q = ops.mfma_gemm(hs[x], L.qkv, 0) if (impl[x][2] and L.qkv_bias is None) else \
-                    ops.linear(hs[x], L.qkv, L.qkv_bias)
-                o = torch.empty(rows[x], c.q_size, device=dev, dtype=h.dtype)
-                q.record_stream(S)
-                o.record_stream(S)
-                qkv[x], att[x] = q, o
-                eq[x].record(G)
-                with torch.cuda.stream(S):
-                    S.wait_event(eq[x])
-                    self.attention(i, q, metas[x], out=o)
-                    ea[x].record(S)
-
-            def post(x, i):
-                L = self.layers[i]
-                G.wait_event(ea[x])
-                hh = ops.mfma_gemm(att[x], L.o, 0) if impl[x][3] else ops.linear(att[x], L.o)
-                ops.fused_add_rmsnorm(hh, res[x], L.post_norm, eps)
-                act = ops.mfma_gemm(hh, L.gate_up, 1) if impl[x][0] else ops.silu_mul(ops.linear(hh, L.gate_up))
-                hs[x] = ops.mfma_gemm(act, L.down, 0) if impl[x][1] else ops.linear(act, L.down)
-
-            with torch.cuda.stream(G):
-                pre(0, 0)
-                pre(1, 0)
-                for i in range(n):
-                    for x in (0, 1):
-                        post(x, i)
-                        if i + 1 < n:
-                            pre(x, i + 1)
-                out_h = torch.cat(hs, 0)
-                out_r = torch.cat(res, 0)
-        finally:
-            ops.set_gemm_cus(0)
-        main.wait_stream(G)
-        out_h.record_stream(main)
-        out_r.record_stream(main)
-        return out_h, out_r
-
     def _forward_layers_quant(self, h: torch.Tensor, meta: AttnMeta, residual: Optional[torch.Tensor] = None,
                               trim_last: Optional[torch.Tensor] = None):
-        """The layers of a weight-quantised model: norm -> linear -> attention -> linear -> norm ->
-        SwiGLU(linear) -> linear, every projection through ``ops.linear`` (the W8A16 kernel for
-        decode-sized steps, dequantise + bf16 GEMM otherwise).  No fused-norm, fused-decode, TBO or
-        MFMA-table layers: those read bf16 weights."""
-        eps = self.cfg.rms_eps
-        for i, L in enumerate(self.layers):
-            if residual is None:
-                residual = h
-                h = ops.rmsnorm(h, L.in_norm, eps)
-            else:
-                ops.fused_add_rmsnorm(h, residual, L.in_norm, eps)
-            attn = self.attention(i, ops.linear(h, L.qkv, L.qkv_bias), meta)
-            if trim_last is not None and i == len(self.layers) - 1:
-                attn = attn.index_select(0, trim_last)
-                residual = residual.index_select(0, trim_last)
-            h = ops.linear(attn, L.o)
-            if self.reduce is not None:
-                self.reduce(h)
-            ops.fused_add_rmsnorm(h, residual, L.post_norm, eps)
-            h = ops.linear(ops.silu_mul(ops.linear(h, L.gate_up)), L.down)
-            if self.reduce is not None:
-                self.reduce(h)
-            if self.capture_layers and (self.layer_start + i) in self.capture_layers:
-                self.captured[self.layer_start + i] = h + residual
-            if self.layer_hook is not None:
-                self.layer_hook(self.layer_start + i)
-        return h, residual
+        """The layers of a weight-quantised model: the unfused loop with no row padding and every
+        projection through ``ops.linear`` (the W8A16 kernel for decode-sized steps, dequantise +
+        bf16 GEMM otherwise).  No fused-norm, fused-decode or MFMA-table layers: those read bf16
+        weights."""
+        return self._unfused_layers(h, meta, residual, trim_last, h.shape[0])
 
     def forward_layers(self, h: torch.Tensor, meta: AttnMeta, residual: Optional[torch.Tensor] = None,
                        trim_last: Optional[torch.Tensor] = None):
@@ -722,65 +577,46 @@ class LlamaModel:
         output is only needed for those rows (the rows that produce logits), so
         after its attention — which has written every row's K/V — its o-proj and
         MLP run on those rows alone and the returned (h, residual) hold just them."""
-        c = self.cfg
-        eps = c.rms_eps
         T = h.shape[0]
         if self.weight_quant:
             return self._forward_layers_quant(h, meta, residual, trim_last)
-        if self.layers:
-            split = self._tbo_ok(h, meta, trim_last)
-            if split is not None:
-                return self._forward_layers_tbo(h, meta, residual, split)
-            if self._fold_ok(h):
-                return self._forward_layers_folded(h, meta, residual, trim_last)
-            fq, fg = self._fused_decode(h, meta)
-            if fq or fg:
-                h, residual = self._forward_layers_fused(h, meta, residual, fq, fg)
-                if trim_last is not None:     # same contract as the unfused path: only the logits rows
-                    h, residual = h.index_select(0, trim_last), residual.index_select(0, trim_last)
-                return h, residual
-        Mp = self._mlp_rows(T, h) if self.layers else T
+        if not self.layers:
+            return h, residual
+        if self._fold_ok(h):
+            return self._forward_layers_folded(h, meta, residual, trim_last)
+        fq, fg = self._fused_decode(h, meta)
+        if fq or fg:
+            h, residual = self._forward_layers_fused(h, meta, residual, fq, fg)
+            if trim_last is not None:     # same contract as the unfused path: only the logits rows
+                h, residual = h.index_select(0, trim_last), residual.index_select(0, trim_last)
+            return h, residual
+        Mp = self._mlp_rows(T, h)
         # hand-written MFMA GEMMs where the start-up table measured them faster (dgi.runtime.gemm_pad)
-        mfma_gu, mfma_dn = self.mlp_impl(Mp) if (self.mlp_impl is not None and self.layers) else (False, False)
-        mfma_q, mfma_o = self.proj_impl(T) if (self.proj_impl is not None and self.layers and h.is_cuda
-                                               and not torch.cuda.is_current_stream_capturing()) else (False, False)
-        hfull = None
+        mlp = self.mlp_impl(Mp) if self.mlp_impl is not None else (False, False)
+        proj = self.proj_impl(T) if (self.proj_impl is not None and h.is_cuda
+                                     and not torch.cuda.is_current_stream_capturing()) else (False, False)
+        return self._unfused_layers(h, meta, residual, trim_last, Mp, mlp, proj)
+
+    def _unfused_layers(self, h: torch.Tensor, meta: AttnMeta, residual: Optional[torch.Tensor],
+                        trim_last: Optional[torch.Tensor], Mp: int, mlp: tuple = (False, False),
+                        proj: tuple = (False, False)):
+        """norm -> QKV -> attention -> o-proj -> add + norm -> SwiGLU(gate_up) -> down, per layer.
+        ``Mp`` > T: the MLP runs on Mp rows of ``_pad_buf`` (``_mlp_rows`` zeroed the pad rows) whose
+        first T the o-proj writes.  ``mlp`` / ``proj``: (gate_up, down) / (QKV, o-proj) on the MFMA
+        kernel rather than ``ops.linear``."""
+        eps = self.cfg.rms_eps
+        T = h.shape[0]
+        (mfma_gu, mfma_dn), (mfma_q, mfma_o) = mlp, proj
         for i, L in enumerate(self.layers):
-            if residual is None:
-                residual = h
-                h = ops.rmsnorm(h, L.in_norm, eps)
-            else:
-                ops.fused_add_rmsnorm(h, residual, L.in_norm, eps)
-            if hfull is not None:
-                # the previous MLP ran on Mp padded rows (zeros past T): the QKV GEMM
-                # reuses them, at the row count the start-up table timed for the layer
-                qkv = ops.linear(hfull, L.qkv, L.qkv_bias)[:T]
-            elif mfma_q and L.qkv_bias is None:
+            h, residual = self._first_norm(h, residual, L)
+            if mfma_q and L.qkv_bias is None:
                 qkv = ops.mfma_gemm(h, L.qkv, 0)
             else:
                 qkv = ops.linear(h, L.qkv, L.qkv_bias)
-            last = trim_last is not None and i == len(self.layers) - 1
-            attn_pad = Mp > T and OPROJ_PAD and not last
-            attn = self.attention(i, qkv, meta, out=self._attn_buf[:T] if attn_pad else None)
-            if last:
-                attn = attn.index_select(0, trim_last)
-                residual = residual.index_select(0, trim_last)
-                h = ops.linear(attn, L.o)
-                if self.reduce is not None:
-                    self.reduce(h)
-                ops.fused_add_rmsnorm(h, residual, L.post_norm, eps)
-                h = ops.linear(ops.silu_mul(ops.linear(h, L.gate_up)), L.down)
-                if self.reduce is not None:
-                    self.reduce(h)
-                if self.layer_hook is not None:
-                    self.layer_hook(self.layer_start + i)
-                break
-            if attn_pad:
-                # attention wrote the first T rows of a zero-padded buffer: the o-proj runs on
-                # all Mp rows (zeros in, zeros out past T) straight into the MLP's input
-                torch.matmul(self._attn_buf[:Mp], L.o.t(), out=self._pad_buf[:Mp])
-                h = self._pad_buf[:T]
-            elif Mp > T:
+            attn = self.attention(i, qkv, meta)
+            if trim_last is not None and i == len(self.layers) - 1:
+                return self._trimmed_tail(i, L, attn, residual, trim_last)
+            if Mp > T:
                 # o-proj writes the first T rows of the padded MLP input
                 h = ops.mfma_gemm(attn, L.o, 0, out=self._pad_buf[:T]) if mfma_o else \
                     torch.matmul(attn, L.o.t(), out=self._pad_buf[:T])
@@ -793,14 +629,10 @@ class LlamaModel:
             act = ops.mfma_gemm(x, L.gate_up, 1) if mfma_gu else ops.silu_mul(ops.linear(x, L.gate_up))
             h = ops.mfma_gemm(act, L.down, 0) if mfma_dn else ops.linear(act, L.down)
             if Mp > T:
-                hfull = h if QKV_PAD else None
                 h = h[:T]
             if self.reduce is not None:
                 self.reduce(h)
-            if self.capture_layers and (self.layer_start + i) in self.capture_layers:
-                self.captured[self.layer_start + i] = h + residual
-            if self.layer_hook is not None:
-                self.layer_hook(self.layer_start + i)
+            self._end_layer(i, h, residual)
         return h, residual
 
     def embed_tokens(self, input_ids: torch.Tensor) -> torch.Tensor:

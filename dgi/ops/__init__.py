@@ -656,13 +656,6 @@ def mfma_gemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
             and x.shape[1] % 64 == 0 and x.data_ptr() % 16 == 0 and x.shape[0] * x.stride(0) < (1 << 31))
 
 
-def set_gemm_cus(cus: int) -> None:
-    """CUs the MFMA GEMM's persistent / split-K launches size their grid for (0 = all of the
-    device's): GEMMs issued on a CU-masked stream (two-batch overlap) set its CU count."""
-    if native_available():
-        torch.ops.dgi.set_gemm_cus(int(cus))
-
-
 def gemm_split_timeouts(reset: bool = False) -> int:
     """Split-K waits of the MFMA GEMM on the current device that ran out since the last reset
     (the last piece of a tile waits, bounded, for the other pieces' slabs; a timeout means a wrong
@@ -685,8 +678,8 @@ def mfma_gemm(x: torch.Tensor, w: torch.Tensor, epi: int = 0, out: Optional[torc
     ``overlap`` False: no cross-tile prologue / epilogue overlap (A/B).
     ``sched`` 1, or a K that is no multiple of 128 or below 256: the
     simple kernel (one barrier per K step), the bit-exact reference of
-    the ping-pong kernel; 0: that kernel in compiler order; 4: the
-    128 x 128 half tile (``epi`` 0; both kept for measurements)."""
+    the ping-pong kernel; 0: that kernel in compiler order (kept for
+    measurements)."""
     M = x.shape[0]
     N = w.shape[0] // 2 if epi == 1 else w.shape[0]
     if mfma_gemm_ok(x, w):

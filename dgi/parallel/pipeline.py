@@ -66,16 +66,10 @@ PREBUILD = os.environ.get("DGI_PP_PREBUILD", "1") == "1"
 def pipeline_buckets(mb_cap: int) -> tuple:
     """Decode microbatch sizes captured as stage graphs: the engine defaults
     plus every multiple of 64 up to the microbatch cap (70B decode pipelines
-    run 768-row microbatches).  With two-batch overlap on (``llama.TBO``) the
-    microbatches it takes (>= ``TBO_MIN_ROWS`` rows) run eagerly on the CU-masked
-    streams instead: a captured graph would drop the masks."""
-    from dgi.models import llama
-    top = mb_cap
-    if llama.TBO:
-        top = min(mb_cap, max(1, llama.TBO_MIN_ROWS - 1))
-    b = set(x for x in DEFAULT_BUCKETS if x <= top)
-    b.update(range(576, top + 1, 64))
-    b.add(top)
+    run 768-row microbatches)."""
+    b = set(x for x in DEFAULT_BUCKETS if x <= mb_cap)
+    b.update(range(576, mb_cap + 1, 64))
+    b.add(mb_cap)
     return tuple(sorted(b))
 
 

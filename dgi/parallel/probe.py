@@ -116,9 +116,7 @@ def run_probe(model: str, device: str, prompt_len: int = 512, output_len: int = 
               decode_rows=(576, 768), mixed_rows: int = 384, layers=(4, 8), steps: int = 8,
               seed: int = 0, prefill_more=(1024,)) -> ProbeResult:
     """Also times prefill steps of each size in ``prefill_more`` (the planner picks the step
-    size for TTFT).  Decode rows that take two-batch overlap (``llama.tbo_split``) are timed
-    eagerly on the CU-masked streams, as the decode roles run them."""
-    from dgi.models import llama
+    size for TTFT)."""
     t_start = time.perf_counter()
     base = get_config(model.split("@")[0] if model else model)
     rng = random.Random(seed)
@@ -155,11 +153,10 @@ def run_probe(model: str, device: str, prompt_len: int = 512, output_len: int = 
                     eng.add_request([rng.randrange(1, mc.vocab_size) for _ in range(prompt_len)], one)
             more[mbt][n] = _time_steps(eng, steps, topm_)
             del eng
-        # decode: rows at the mean context, graph-captured like the serving engines (two-batch
-        # overlap steps eagerly: a graph would drop the CU masks)
+        # decode: rows at the mean context, graph-captured like the serving engines
         for rows in decode_rows:
             nb = rows * (ctx // bs + 2 + steps + 4) + 8
-            graphs = device != "cpu" and not (llama.TBO and llama.tbo_split(rows) is not None)
+            graphs = device != "cpu"
             eng = _engine(model, mc, device, rows, max(4096, rows), nb, graphs=graphs, buckets=(rows,))
             _adopt(eng, rows, ctx, rng)
             dec[rows][n] = _time_steps(eng, steps)

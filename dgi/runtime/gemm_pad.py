@@ -8,8 +8,7 @@ step's row count is whatever the scheduler packed, so it lands on both sides
 of those cliffs.
 
 The MLP is row-independent, so its rows can be padded for free as far as
-correctness goes (and so is the next layer's QKV GEMM, which reuses the MLP's
-padded output rows — zeros past T — so the table times it at the same row count): ``MlpPadTable.measure`` times gate_up + SiLU·mul + down for
+correctness goes: ``MlpPadTable.measure`` times gate_up + SiLU·mul + down for
 every multiple of ``step`` rows up to the token budget, and ``pad(T)`` returns
 the row count (a multiple of ``step``, at most ``max_grow`` larger than T)
 with the lowest measured time.  ``LlamaModel.forward_layers`` then lets the
@@ -44,6 +43,8 @@ MFMA_MARGIN = 0.97
 # writes the measured table (scripts/gemm_table_build.py combines passes into the shipped one).
 TABLE_MODE = os.environ.get("DGI_GEMM_TABLE", "auto")
 TUNED_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tuned")
+# "q" / "o": entries of tables saved while the qkv / o-proj could join the padded rows; never
+# measured now (null in the shipped table), still read
 RAW_KEYS = ("front", "front_mfma", "back", "back_mfma", "q", "o", "pq_blas", "pq_mfma", "po_blas", "po_mfma")
 
 
@@ -111,19 +112,14 @@ class MlpPadTable:
 
     @classmethod
     def measure(cls, gate_up: torch.Tensor, down: torch.Tensor, m_min: int = 512, m_max: int = 4096,
-                step: int = 32, reps: int = 3, qkv: Optional[torch.Tensor] = None,
-                o_w: Optional[torch.Tensor] = None, proj_qkv: Optional[torch.Tensor] = None,
+                step: int = 32, reps: int = 3, proj_qkv: Optional[torch.Tensor] = None,
                 proj_o: Optional[torch.Tensor] = None) -> "MlpPadTable":
-        """``qkv`` / ``o_w``: the next layer's QKV GEMM and this layer's o-proj run on
-        the same padded rows (``LlamaModel.forward_layers``), so their times join
-        the objective.  ``proj_qkv`` / ``proj_o``: the (bias-free) QKV and o-proj
-        weights whose implementation is chosen per row count (``proj_impl``)."""
+        """``proj_qkv`` / ``proj_o``: the (bias-free) QKV and o-proj weights whose
+        implementation is chosen per row count (``proj_impl``)."""
         from dgi import ops
         H = gate_up.shape[1]
         x = torch.randn(m_max, H, device=gate_up.device, dtype=gate_up.dtype) * 0.1
         a = torch.randn(m_max, gate_up.shape[0] // 2, device=gate_up.device, dtype=gate_up.dtype) * 0.1
-        ao = torch.randn(m_max, o_w.shape[1], device=gate_up.device, dtype=gate_up.dtype) * 0.1 \
-            if o_w is not None else None
         pa = torch.randn(m_max, proj_o.shape[1], device=gate_up.device, dtype=gate_up.dtype) * 0.1 \
             if proj_o is not None else None
         grid = list(range(m_min, m_max + 1, step))
@@ -152,8 +148,6 @@ class MlpPadTable:
                 r["front_mfma"] = timed(lambda: ops.mfma_gemm(x[:m], gate_up, 1))
             if mfma_down:
                 r["back_mfma"] = timed(lambda: ops.mfma_gemm(a[:m], down, 0))
-            r["q"] = timed(lambda: ops.linear(x[:m], qkv)) if qkv is not None else None
-            r["o"] = timed(lambda: ops.linear(ao[:m], o_w)) if o_w is not None else None
             if use_mfma and proj_qkv is not None and ops.mfma_gemm_ok(x, proj_qkv):
                 r["pq_mfma"] = timed(lambda: ops.mfma_gemm(x[:m], proj_qkv, 0))
                 r["pq_blas"] = timed(lambda: ops.linear(x[:m], proj_qkv))
@@ -221,11 +215,11 @@ _TABLES: dict = {}      # (shapes, device, step) -> (m_max, table): one measurem
 
 
 def table_key(model, step: int, m_min: int) -> dict:
-    from dgi.models import llama
     L = model.layers[0]
+    # "qkv_pad" / "oproj_pad": switches that are gone; the literals keep the shipped table's key and name
     return {"gate_up": list(L.gate_up.shape), "down": list(L.down.shape), "qkv": list(L.qkv.shape),
             "o": list(L.o.shape), "qkv_bias": L.qkv_bias is not None, "step": step, "m_min": m_min,
-            "qkv_pad": llama.QKV_PAD, "oproj_pad": llama.OPROJ_PAD, "mfma": MFMA_GEMM}
+            "qkv_pad": False, "oproj_pad": False, "mfma": MFMA_GEMM}
 
 
 def tuned_path(key: dict) -> str:
@@ -263,7 +257,7 @@ def load_tuned(key: dict, m_max: int, device=None) -> Optional[MlpPadTable]:
     return MlpPadTable.from_json(d)
 
 
-M_MIN = 256        # two-batch-overlap halves run 256-row GEMMs
+M_MIN = 256        # first row count of the table (part of the shipped table's key)
 
 
 def build_for_model(model, m_max: int, step: int = 32) -> Optional[MlpPadTable]:
@@ -280,9 +274,8 @@ def build_for_model(model, m_max: int, step: int = 32) -> Optional[MlpPadTable]:
     L = layers[0]
     if L.gate_up.device.type != "cuda" or m_max < 1024:
         return None
-    from dgi.models import llama
     key = (tuple(L.gate_up.shape), tuple(L.down.shape), tuple(L.qkv.shape), tuple(L.o.shape), L.qkv_bias is None,
-           str(L.gate_up.device), L.gate_up.dtype, step, llama.QKV_PAD, llama.OPROJ_PAD)
+           str(L.gate_up.device), L.gate_up.dtype, step)
     hit = _TABLES.get(key)
     if hit is not None and hit[0] >= m_max:
         return hit[1]
@@ -290,7 +283,6 @@ def build_for_model(model, m_max: int, step: int = 32) -> Optional[MlpPadTable]:
     t = load_tuned(tk, m_max, L.gate_up.device) if TABLE_MODE == "auto" else None
     if t is None:
         t = MlpPadTable.measure(L.gate_up, L.down, m_min=M_MIN, m_max=m_max, step=step,
-                                qkv=L.qkv if llama.QKV_PAD else None, o_w=L.o if llama.OPROJ_PAD else None,
                                 proj_qkv=L.qkv if L.qkv_bias is None else None, proj_o=L.o)
         save = os.environ.get("DGI_GEMM_TABLE_SAVE")
         if save:

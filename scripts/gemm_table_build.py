@@ -33,11 +33,9 @@ def main():
     mc = dataclasses.replace(get_config(a.model), num_layers=1)
     model = LlamaModel(mc, "cuda", layer_start=0, layer_end=1, has_embed=False, has_head=False)
     L = model.layers[0]
-    from dgi.models import llama
     runs = []
     for i in range(a.passes):
         t = gemm_pad.MlpPadTable.measure(L.gate_up, L.down, m_min=gemm_pad.M_MIN, m_max=a.m_max, step=32,
-                                         qkv=L.qkv if llama.QKV_PAD else None, o_w=L.o if llama.OPROJ_PAD else None,
                                          proj_qkv=L.qkv if L.qkv_bias is None else None, proj_o=L.o)
         runs.append(t)
         print(json.dumps({"pass": i, "gate_up_mfma": sum(f for f, _ in t.impls), "down_mfma": sum(b for _, b in t.impls),

@@ -28,7 +28,7 @@ SHAPES = {  # name: (N, K)
 MS = [int(x) for x in os.environ.get("GEMM_MS", "512,1024,1536,1792,2048,4096").split(",")]
 ROUNDS = int(os.environ.get("GEMM_ROUNDS", "7"))
 ITERS = int(os.environ.get("GEMM_ITERS", "10"))
-# schedule ids (0, 1, 3, 4); "3k" = schedule 3 with split-K off,
+# schedule ids (0, 1, 3); "3k" = schedule 3 with split-K off,
 # "3h" / "3f" = schedule 3 with two 32-MFMA / four 16-MFMA phases per K tile (default: by M),
 # "3n" = schedule 3 without the cross-tile prologue / epilogue overlap
 SCHEDS = os.environ.get("GEMM_SCHEDS", "1,0,3").split(",")

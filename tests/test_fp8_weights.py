@@ -88,7 +88,7 @@ def test_cpu_engine_matches_dequantised_model(monkeypatch):
         calls["quant"] += 1
         return orig(self, *a, **k)
     monkeypatch.setattr(LlamaModel, "_forward_layers_quant", spy)
-    for name in ("_forward_layers_tbo", "_forward_layers_folded", "_forward_layers_fused", "_mlp_rows", "fold_norms"):
+    for name in ("_forward_layers_folded", "_forward_layers_fused", "_mlp_rows", "fold_norms"):
         def other(self, *a, _n=name, _o=getattr(LlamaModel, name), **k):
             calls["other"].append((_n, self.weight_quant))
             return _o(self, *a, **k)

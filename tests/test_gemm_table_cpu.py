@@ -4,6 +4,9 @@ to the shape key, and ``load_tuned`` refuses a table whose tag differs."""
 import glob
 import json
 import os
+from types import SimpleNamespace
+
+import torch
 
 from dgi.runtime import gemm_pad
 
@@ -15,6 +18,11 @@ def test_shipped_table_is_tagged_for_mi355x():
         d = json.load(open(p))
         assert d["device"]["arch"] == "gfx950" and d["device"]["hip"]
         assert gemm_pad.tuned_path(d["key"]) == p          # the file name still hashes the key only
+        # a model of the key's shapes still derives this very key (and so finds this file)
+        k = d["key"]
+        L = SimpleNamespace(qkv_bias=torch.empty(0) if k["qkv_bias"] else None,
+                            **{n: torch.empty(k[n], device="meta") for n in ("gate_up", "down", "qkv", "o")})
+        assert gemm_pad.table_key(SimpleNamespace(layers=[L]), k["step"], gemm_pad.M_MIN) == k
 
 
 def test_load_tuned_refuses_another_device(tmp_path, monkeypatch):

@@ -784,90 +784,6 @@ def test_decode_lookahead_admission_abort_and_page_exhaustion():
     assert run(True, num_blocks=need) == run(False, num_blocks=need) == plain
 
 
-@pytest.mark.parametrize("rows", [768, 1024])
-def test_two_batch_overlap_decode_step_matches_one_batch(rows, monkeypatch):
-    """Two-batch overlap (CU-masked GEMM and attention streams, dgi.models.llama
-    _forward_layers_tbo) on a pure-decode step gives the logits of the one-batch step
-    (same KV, same rows) up to GEMM blocking, and both are within bf16 tolerance of the
-    fp32 CPU model on a sample of rows."""
-    import random
-    from dgi.engine import EngineConfig, LLMEngine
-    from dgi.models import llama
-    from dgi.models.config import get_config
-    from dgi.models.llama import LlamaModel
-    from dgi.parallel.probe import _adopt
-    mc = get_config("llama-tiny-hd128")
-    src = LlamaModel(mc, "cpu", seed=21)
-    gm = LlamaModel(mc, "cuda", init="empty").copy_from(src)
-    eng = LLMEngine(EngineConfig(model="llama-tiny-hd128", device="cuda", num_blocks=rows * 8 + 16,
-                                 max_num_seqs=rows, max_model_len=512, max_num_batched_tokens=2048, use_graphs=False,
-                                 enable_prefix_caching=False), model_cfg=mc, model=gm)
-    torch.manual_seed(5)
-    eng.pool.kv.normal_(0, 1)
-    _adopt(eng, rows, 90, random.Random(1))
-    sb = eng.scheduler.schedule()
-    assert len(sb.decode) == rows and not sb.prefill
-    flat, hdr, _ = eng.runner.build_host(sb)
-    ids, meta, _ = eng.runner.meta_from_device(eng.runner.to_device(flat), hdr)
-    monkeypatch.setattr(llama, "TBO", False)
-    ref = eng.model.forward(meta, input_ids=ids).float()
-    monkeypatch.setattr(llama, "TBO", True)
-    assert eng.model._tbo_ok(torch.empty(rows, 8, device="cuda", dtype=torch.bfloat16), meta, None) == \
-        llama.tbo_split(rows)
-    got = eng.model.forward(meta, input_ids=ids).float()
-    torch.cuda.synchronize()
-    scale = float(ref.abs().max())
-    assert float((got - ref).abs().max()) <= 0.02 * scale
-    # a sample of rows against the fp32 CPU model over the same KV pages
-    pick = [0, 1, rows // 2, rows - 1]
-    kv_cpu = eng.pool.kv.float().cpu()
-    for r in pick:
-        req = sb.decode[r]
-        ctx = req.num_computed + 1
-        blocks = req.blocks[: (ctx + 15) // 16]
-        lg = _cpu_decode_row(src, kv_cpu, blocks, ctx, int(ids[r]))
-        assert float((got[r].cpu() - lg).abs().max()) <= 0.03 * float(lg.abs().max()) + 0.03
-
-
-def _cpu_decode_row(model, kv, blocks, ctx, tok):
-    """fp32 CPU logits of one decode row at position ctx - 1 over paged KV ``kv`` (pages
-    ``blocks``; the row's own K/V is computed here, the rest read from the pages)."""
-    import math as _m
-    c = model.cfg
-    x = model.embed[tok].float()[None]
-    pos = torch.tensor([ctx - 1])
-    cs = ops.rope_cos_sin(c.rope_dim, c.max_position, c.rope_theta, c.rope_scaling)
-    res = None
-    for i, L in enumerate(model.layers):
-        if res is None:
-            res = x
-            h = ops.rmsnorm_ref(x, L.in_norm.float(), c.rms_eps)
-        else:
-            res = x + res
-            h = ops.rmsnorm_ref(res, L.in_norm.float(), c.rms_eps)
-        qkv = h @ L.qkv.float().t()
-        nh, nkv, hd = c.num_heads, c.num_kv_heads, c.head_dim
-        q = qkv[:, : nh * hd].view(1, nh, hd)
-        k = qkv[:, nh * hd:(nh + nkv) * hd].view(1, nkv, hd)
-        v = qkv[:, (nh + nkv) * hd:].view(1, nkv, hd)
-        q = ops._rope(q, cs[pos], 0)
-        k = ops._rope(k, cs[pos], 0)
-        K = kv[i, 0][blocks].permute(0, 2, 1, 3).reshape(-1, nkv, hd)[:ctx].clone()
-        V = kv[i, 1][blocks].permute(0, 2, 1, 3).reshape(-1, nkv, hd)[:ctx].clone()
-        K[ctx - 1], V[ctx - 1] = k[0], v[0]
-        G = nh // nkv
-        s = torch.einsum("hgd,thd->hgt", q.view(nkv, G, hd), K) / _m.sqrt(hd)
-        o = torch.einsum("hgt,thd->hgd", torch.softmax(s, -1), V).reshape(1, nh * hd)
-        x = o @ L.o.float().t()
-        res = x + res
-        h = ops.rmsnorm_ref(res, L.post_norm.float(), c.rms_eps)
-        gu = h @ L.gate_up.float().t()
-        I = gu.shape[1] // 2
-        x = (torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]) @ L.down.float().t()
-    h = ops.rmsnorm_ref(x + res, model.norm.float(), c.rms_eps)
-    return (h @ model.lm_head.float().t())[0]
-
-
 @pytest.mark.parametrize("sampled,eos", [(False, False), (True, False), (False, True)])
 def test_mixed_step_lookahead_matches_plain_steps(sampled, eos):
     """Mixed-step lookahead (step N+1 scheduled and launched before step N's tokens are back,

@@ -47,23 +47,7 @@ def test_mfma_gemm_matches_fp32(M, N, K, epi, sched):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("M,N,K", [(1, 256, 64), (100, 512, 256), (128, 256, 128), (300, 768, 512),
-                                   (512, 1280, 1024), (777, 512, 8192), (512, 10240, 512)])
-def test_mfma_gemm_half_tile_matches_fp32(M, N, K):
-    """Schedule 4: the 128 x 128 half-tile kernel (plain GEMM) against fp32, M tails included."""
-    ops.load_native(required=True)
-    x = _rand(M, K, device="cuda", seed=M + K)
-    w = _rand(N, K, device="cuda", scale=0.05, seed=N)
-    ref = ops.mfma_gemm_ref(x, w, 0).float()
-    got = ops.mfma_gemm(x, w, 0, sched=4)
-    torch.cuda.synchronize()
-    err = (got.float() - ref).abs()
-    tol = 2e-2 * ref.abs().max().item() + 1e-3
-    assert err.max().item() <= tol, (err.max().item(), tol)
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("sched", [0, 1, 3, 4])
+@pytest.mark.parametrize("sched", [0, 1, 3])
 def test_mfma_gemm_strided_rows_and_asymmetric_operands(sched):
     """A = row slice of a wider buffer (ldx > K) and an asymmetric W: catches
     row/column swaps in the C write and ldx handling."""
@@ -127,32 +111,6 @@ def test_mfma_gemm_splitk_matches_fp32_and_is_deterministic(M, N, K, epi, stream
     for _ in range(6):
         assert torch.equal(ops.mfma_gemm(x, w, epi, sched=3, streamk=streamk, phases=phases), got)
     assert ops.gemm_split_timeouts(reset=True) == 0
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("cus,N", [(160, 10240), (192, 8192), (128, 4096)])
-def test_mfma_gemm_splitk_on_a_cu_limited_grid(cus, N):
-    """Split-K on a grid sized for fewer CUs (``set_gemm_cus``, what a CU-masked two-batch-overlap
-    stream uses): 2 / 3 / 4 pieces per tile, the "written" counters at [P + t] of a smaller P, the
-    last piece's registers folded in piece order.  Matches fp32, bit-identical on repeats, and the
-    counters are back to zero for the next full-grid launch."""
-    ops.load_native(required=True)
-    x = _rand(512, 2048, device="cuda", seed=11)
-    w = _rand(N, 2048, device="cuda", scale=0.05, seed=12)
-    ref = ops.mfma_gemm_ref(x, w, 0).float()
-    ops.set_gemm_cus(cus)
-    try:
-        got = ops.mfma_gemm(x, w, 0, sched=3)
-        again = [ops.mfma_gemm(x, w, 0, sched=3) for _ in range(4)]
-    finally:
-        ops.set_gemm_cus(0)
-    full = ops.mfma_gemm(x, w, 0, sched=3)
-    torch.cuda.synchronize()
-    tol = 2e-2 * ref.abs().max().item() + 1e-3
-    assert (got.float() - ref).abs().max().item() <= tol
-    assert all(torch.equal(a, got) for a in again)
-    assert (full.float() - ref).abs().max().item() <= tol
-    assert ops.gemm_split_timeouts(reset=True) == 0        # no last piece's wait ran out
 
 
 # ---------------------------------------------------------------------------

@@ -378,3 +378,43 @@ def test_fused_norm_layer_composition_matches_unfused_cpu(monkeypatch, name):
     assert torch.allclose(l0, l1, atol=1e-3, rtol=1e-3) and torch.allclose(l1[-1], f1[-1], atol=1e-3, rtol=1e-3)
     for k in (0, mc.num_layers - 1):
         assert torch.allclose(c0[k], c1[k], atol=1e-3, rtol=1e-3)
+
+
+def test_trimmed_last_layer_is_bit_identical_on_a_mixed_step(monkeypatch):
+    """One mixed step (a decode row beside a prompt) with fewer logits rows than rows: the shared
+    trimmed-last-layer tail gives exactly the untrimmed layers' logits, on the plain loop and on
+    the weight-quantised loop (``_forward_layers_quant``).  The step has 7 rows: every op of the
+    tail is row-independent, and the CPU BLAS behind ``ops.linear`` rounds a row the same way for
+    any row count up to 8 (from 16 rows on it blocks differently and single rows move by ~2e-6,
+    which would be the BLAS's difference, not the layers')."""
+    import dgi.models.llama as llama
+    from dgi.engine import EngineConfig, LLMEngine
+    from dgi.models.config import get_config
+    from dgi.models.llama import LlamaModel
+    from dgi.sched.request import SamplingParams
+    seen = []
+    for name in ("_forward_layers_quant", "_trimmed_tail"):
+        monkeypatch.setattr(LlamaModel, name, lambda self, *a, _n=name, _o=getattr(LlamaModel, name), **k:
+                            seen.append(_n) or _o(self, *a, **k))
+    sp = SamplingParams(max_tokens=8, temperature=0.0, ignore_eos=True)
+    for weight_quant in (None, "fp8"):
+        e = LLMEngine(EngineConfig(model="llama-tiny-hd128", device="cpu", dtype=torch.float32, num_blocks=64,
+                                   max_num_seqs=4, max_model_len=256, max_num_batched_tokens=64, use_graphs=False,
+                                   enable_prefix_caching=False, seed=3, weight_quant=weight_quant),
+                      model_cfg=get_config("llama-tiny-hd128"))
+        e.add_request([1, 5, 9, 300, 17], sp)
+        e.step()
+        e.add_request([7, 8, 9, 10, 11, 12], sp)
+        sb = e.scheduler.schedule()
+        assert len(sb.decode) == 1 and len(sb.prefill) == 1
+        flat, hdr, _ = e.runner.build_host(sb)
+        ids, meta, _ = e.runner.meta_from_device(e.runner.to_device(flat), hdr)
+        assert meta.logits_indices.shape[0] == 2 and ids.shape[0] == 7
+        logits = {}
+        for flag in (True, False):
+            monkeypatch.setattr(llama, "TRIM_LAST_LAYER", flag)
+            seen.clear()
+            logits[flag] = e.model.forward(meta, input_ids=ids).clone()
+            assert ("_trimmed_tail" in seen) == flag
+            assert ("_forward_layers_quant" in seen) == (weight_quant is not None)
+        assert logits[True].shape[0] == 2 and torch.equal(logits[True], logits[False])

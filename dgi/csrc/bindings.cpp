@@ -92,6 +92,15 @@ void check_i32(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
+// int32 [rows, width] whose rows are dense but may lie further apart than their width (a column
+// slice of a wider persistent table): the kernels take the row stride
+void check_i32_rows(const at::Tensor& t, const char* name) {
+  check_dev(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
+  TORCH_CHECK(t.dim() == 2 && (t.size(1) <= 1 || t.stride(1) == 1) &&
+                  (t.size(0) <= 1 || t.stride(0) >= t.size(1)),
+              name, " must be 2-D with dense rows");
+}
 
 void rmsnorm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, double eps) {
   check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
@@ -141,7 +150,7 @@ void paged_decode(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cache
                   int64_t nh, int64_t nkv, int64_t max_splits, int64_t part_size, double scale,
                   const c10::optional<at::Tensor>& counters) {
   check_bf16(out, "out"); check_bf16(q, "q"); check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
-  check_i32(block_tables, "block_tables"); check_i32(context_lens, "context_lens");
+  check_i32_rows(block_tables, "block_tables"); check_i32(context_lens, "context_lens");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1 && out.dim() == 2 && out.stride(1) == 1);
   const int hd = (int)k_cache.size(3);
   const int B = (int)q.size(0);
@@ -175,7 +184,7 @@ void paged_prefill(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cach
                    const at::Tensor& tiles, int64_t nh, int64_t nkv, double scale,
                    const c10::optional<at::Tensor>& tree_mask, int64_t tree_n, int64_t tile_rows) {
   check_bf16(out, "out"); check_bf16(q, "q"); check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
-  check_i32(block_tables, "block_tables"); check_i32(cu_seqlens_q, "cu_seqlens_q");
+  check_i32_rows(block_tables, "block_tables"); check_i32(cu_seqlens_q, "cu_seqlens_q");
   check_i32(context_lens, "context_lens"); check_i32(tiles, "tiles");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1 && out.dim() == 2 && out.stride(1) == 1);
   const int hd = (int)k_cache.size(3);

@@ -5,9 +5,18 @@
 // small per-row kernels.  On MI355X each of those small kernels costs 4-10 us
 // of dispatch + ramp for a few KB of work (profiles/r1_decode8b_b1_kernel_stats.md:
 // RMSNorm x2, RoPE+KV write, SiLU·mul = ~20 us per layer of a 4.1 ms 8B step).
-// This kernel is the skinny GEMM of skinny_gemm.hip (16-column tiles, NW waves
-// splitting K, weight fragments streamed straight to VGPRs as MFMA B operands)
-// with two column tiles per workgroup — a *pair* (c0, c1 = c0 + pair_off) — and:
+// These kernels are the skinny GEMM of skinny_gemm.hip (NW waves splitting K, weight
+// fragments streamed straight to VGPRs as MFMA B operands through a register ring) working
+// on column *pairs* (c0, c1 = c0 + pair_off), in three shapes (the launch configs at the
+// bottom; what each was measured against is under profiles/, see ops.FUSED_CFGS):
+//
+//  * fused_skinny_kernel: one workgroup per pair of 16-row weight tiles (c0 + r, c1 + r);
+//  * fused_skinny_persist_kernel: one workgroup per CU streams consecutive 8 + 8 row pair
+//    tiles through one ring and stages X once;
+//  * fused_skinny_quarter_kernel: the same on quarter pairs of 4 + 4 rows, which balances
+//    launches of 1.5 pair tiles per CU.
+//
+// Around the GEMM:
 //
 //  prologue PRO (the GEMM input is the normalised residual stream):
 //    1: x = rmsnorm(h) * gamma                   (first layer: residual = h)
@@ -59,17 +68,9 @@ struct FusedArgs {
   uint16_t* k_cache;  // [blocks, nkv, bs, 128]
   uint16_t* v_cache;
   int nh, nkv, bs_log2;
-  // KS > 1: per-tile fp32 partials [tile][KS][64 lanes] and arrival counters (zero between launches)
-  float* ws;
-  int* cnt;
 };
 
-// buffer resource word 3 of a raw byte-addressed buffer, and the write-through (sc1) policy bit
-constexpr int kRsrcWord3 = 0x00020000;
-constexpr int kSc1 = 16;
-constexpr int kKsMaxTiles = 4096;
-constexpr int kKsMax = 2;
-
+// Weight fragments of U K-steps for TW 16-row tiles.
 template <int U, int TW>
 struct Frag {
   u32x4 w[U][TW][2];
@@ -197,35 +198,32 @@ __device__ __forceinline__ void store_rows(const FusedArgs& a, int row0, int row
   }
 }
 
-// Epilogue of one column pair on wave 0: (v0, v1) = rows (c0 + rr, c1 + rr).
-template <int TW, int EPI>
-__device__ __forceinline__ void store_pair(const FusedArgs& a, int c0, int c1, int r, int g, bool lo,
-                                           const f32x4& v0, const f32x4& v1) {
-  const int rr = TW == 2 ? r : (r & 7);
-  const float b0 = (TW == 2 && a.bias) ? bf16_to_f32(a.bias[c0 + r]) : 0.f;
-  const float b1 = (TW == 2 && a.bias) ? bf16_to_f32(a.bias[c1 + r]) : 0.f;
-  // TW 1: lanes r < 8 store the pair's first half, r >= 8 the second
-  store_rows<EPI>(a, c0 + rr, c1 + rr, g, TW == 2 || lo, TW == 2 || !lo, b0, b1, v0, v1);
+// Epilogue of a pair of 16-row tiles on wave 0: (v0, v1) = rows (c0 + r, c1 + r).
+template <int EPI>
+__device__ __forceinline__ void store_pair(const FusedArgs& a, int c0, int c1, int r, int g, const f32x4& v0,
+                                           const f32x4& v1) {
+  const float b0 = a.bias ? bf16_to_f32(a.bias[c0 + r]) : 0.f;
+  const float b1 = a.bias ? bf16_to_f32(a.bias[c1 + r]) : 0.f;
+  store_rows<EPI>(a, c0 + r, c1 + r, g, true, true, b0, b1, v0, v1);
 }
 
-// TW: 16-row weight tiles per workgroup.  TW = 2 is the pair (c0 + r, c1 + r);
-// TW = 1 packs both halves of a pair into one tile — lanes r < 8 read rows c0 + r,
-// lanes r >= 8 rows c1 + r - 8 — and swaps the halves with a lane shuffle in the
-// epilogue: half the rows per workgroup, twice the workgroups (qkv on 8B: 384
-// instead of 192 on 256 CUs).  D: load groups in flight (register ring); the
-// first D are issued before the X staging.
-// KS > 1 (TW = 1 only) splits K over KS workgroups per pair tile: 8B qkv has 384 pair
-// tiles, 1.5 per CU, so half the CUs stream twice the bytes of the other half; 768
-// half-K workgroups are 3 per CU.  Each part publishes its cross-wave sum (1 KB) with
-// write-through stores and bumps the tile's counter; the last part to arrive sums every
-// part in part order (deterministic) and runs the epilogue.
-template <int NW, int U, int TW, int D, int PRO, int EPI, int KS = 1>
+// Epilogue of an 8 + 8 row pair tile on wave 0: lanes r < 8 store row c0 + r, the others row
+// c1 + r - 8 (the bias is in v0 / v1 already).
+template <int EPI>
+__device__ __forceinline__ void store_half_pair(const FusedArgs& a, int c0, int c1, int r, int g, bool lo,
+                                                const f32x4& v0, const f32x4& v1) {
+  const int rr = r & 7;
+  store_rows<EPI>(a, c0 + rr, c1 + rr, g, lo, !lo, 0.f, 0.f, v0, v1);
+}
+
+// One workgroup per pair of 16-row weight tiles: lane r reads rows c0 + r and c1 + r.
+// D: load groups in flight (register ring); the first D are issued before the X staging.
+template <int NW, int U, int D, int PRO, int EPI>
 __global__ __launch_bounds__(NW * 64) void fused_skinny_kernel(FusedArgs a) {
-  static_assert(KS == 1 || TW == 1, "split-K pairs are one-tile workgroups");
   // normalised X rows live in LDS for the whole kernel: [M][K + 8] bf16 (16-byte
   // row pad keeps the 16-row fragment reads off one bank)
   extern __shared__ __attribute__((aligned(16))) uint16_t xs[];
-  __shared__ f32x4 red[NW][TW][64];
+  __shared__ f32x4 red[NW][2][64];
   __shared__ float s_part[NW][16];
   __shared__ float s_inv[16];
   const int tid = threadIdx.x;
@@ -237,44 +235,29 @@ __global__ __launch_bounds__(NW * 64) void fused_skinny_kernel(FusedArgs a) {
   const int M = a.M;
   const int ldx = K + 8;
   const int bid = blockIdx.x;
-  // KS > 1: the parts of one tile are workgroups 8 apart (one XCD under round-robin
-  // dispatch, so the partials meet in that XCD's L2) when the grid is a multiple of 8 KS
-  int tile = bid, part = 0;
-  if (KS > 1) {
-    if ((gridDim.x % (8 * KS)) == 0) {
-      tile = (bid / (8 * KS)) * 8 + (bid & 7);
-      part = (bid >> 3) % KS;
-    } else {
-      tile = bid / KS;
-      part = bid % KS;
-    }
-  }
-  const int c0 = (tile / a.tpg) * a.gstride + (tile % a.tpg) * (TW == 2 ? 16 : 8);
+  const int c0 = (bid / a.tpg) * a.gstride + (bid % a.tpg) * 16;
   const int c1 = c0 + a.pair_off;
-  const int ngroups = ((K / KS) >> 6) / (NW * U);
-  const size_t lane_k = (size_t)g * 16 + (size_t)w * 64 + (size_t)part * (K / KS);
-  const bool lo = r < 8;
-  const uint16_t* w0 = a.w + (size_t)(TW == 2 ? c0 + r : (lo ? c0 + r : c1 + r - 8)) * K + lane_k;
+  const int ngroups = (K >> 6) / (NW * U);
+  const size_t lane_k = (size_t)g * 16 + (size_t)w * 64;
+  const uint16_t* w0 = a.w + (size_t)(c0 + r) * K + lane_k;
   const uint16_t* w1 = a.w + (size_t)(c1 + r) * K + lane_k;
   const bool xval = r < M;
 
-  auto load = [&](Frag<U, TW>& f, int grp) {
+  auto load = [&](Frag<U, 2>& f, int grp) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const size_t off = ((size_t)grp * NW * U + (size_t)u * NW) * 64;
       const u32x4* p0 = reinterpret_cast<const u32x4*>(w0 + off);
       f.w[u][0][0] = __builtin_nontemporal_load(p0);
       f.w[u][0][1] = __builtin_nontemporal_load(p0 + 1);
-      if (TW == 2) {
-        const u32x4* p1 = reinterpret_cast<const u32x4*>(w1 + off);
-        f.w[u][TW - 1][0] = __builtin_nontemporal_load(p1);
-        f.w[u][TW - 1][1] = __builtin_nontemporal_load(p1 + 1);
-      }
+      const u32x4* p1 = reinterpret_cast<const u32x4*>(w1 + off);
+      f.w[u][1][0] = __builtin_nontemporal_load(p1);
+      f.w[u][1][1] = __builtin_nontemporal_load(p1 + 1);
     }
   };
 
   // the first D groups stream while X is staged
-  Frag<U, TW> ring[D];
+  Frag<U, 2> ring[D];
 #pragma unroll
   for (int d = 0; d < D; ++d)
     if (d < ngroups) load(ring[d], d);
@@ -282,10 +265,10 @@ __global__ __launch_bounds__(NW * 64) void fused_skinny_kernel(FusedArgs a) {
   stage_x<NW, PRO>(a, xs, s_part, s_inv, bid);
 
   const uint16_t* xl = xs + (xval ? r : 0) * ldx + lane_k;
-  f32x4 acc[TW];
+  f32x4 acc[2];
 #pragma unroll
-  for (int nt = 0; nt < TW; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](const Frag<U, TW>& f, int grp) {
+  for (int nt = 0; nt < 2; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto compute = [&](const Frag<U, 2>& f, int grp) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int off = (grp * NW * U + u * NW) * 64;
@@ -295,7 +278,7 @@ __global__ __launch_bounds__(NW * 64) void fused_skinny_kernel(FusedArgs a) {
         xb = *reinterpret_cast<const u32x4*>(xl + off + 8);
       }
 #pragma unroll
-      for (int nt = 0; nt < TW; ++nt) {
+      for (int nt = 0; nt < 2; ++nt) {
         acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xa), as_bf16x8(f.w[u][nt][0]), acc[nt], 0, 0, 0);
         acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xb), as_bf16x8(f.w[u][nt][1]), acc[nt], 0, 0, 0);
       }
@@ -312,49 +295,21 @@ __global__ __launch_bounds__(NW * 64) void fused_skinny_kernel(FusedArgs a) {
   }
 
 #pragma unroll
-  for (int nt = 0; nt < TW; ++nt) red[w][nt][lane] = acc[nt];
+  for (int nt = 0; nt < 2; ++nt) red[w][nt][lane] = acc[nt];
   __syncthreads();
   if (w != 0) return;
-  f32x4 v0 = red[0][0][lane], v1 = red[0][TW - 1][lane];
+  f32x4 v0 = red[0][0][lane], v1 = red[0][1][lane];
 #pragma unroll
   for (int j = 1; j < NW; ++j) {
     v0 += red[j][0][lane];
-    if (TW == 2) v1 += red[j][1][lane];
+    v1 += red[j][1][lane];
   }
-  if (KS > 1) {
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.ws + (size_t)tile * KS * 256), 0, KS * 256 * 4, kRsrcWord3);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v0), rs, (part * 64 + lane) * 16, 0, kSc1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(a.cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    old = __shfl(old, 0);
-    if (old != KS - 1) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (lane == 0) __hip_atomic_store(a.cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    v0 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < KS; ++j)
-      v0 += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (j * 64 + lane) * 16, 0, 0));
-    v1 = v0;
-  }
-  if (TW == 1) {
-    // this lane holds row c0 + r (r < 8) or c1 + r - 8; bring the other half of
-    // the pair over from lane ^ 8 (same row group g) so the epilogue below sees
-    // (v0, v1) = (row c0 + (r & 7), row c1 + (r & 7)) on every lane
-    const float bo = a.bias ? bf16_to_f32(a.bias[lo ? c0 + r : c1 + r - 8]) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float own = v0[i] + bo;
-      const float oth = __shfl_xor(own, 8);
-      v0[i] = lo ? own : oth;
-      v1[i] = lo ? oth : own;
-    }
-  }
-  store_pair<TW, EPI>(a, c0, c1, r, g, lo, v0, v1);
+  store_pair<EPI>(a, c0, c1, r, g, v0, v1);
 }
 
-// Persistent variant (TW = 1): a workgroup owns `tpw` consecutive pair tiles and
+// Persistent variant: a pair tile is ONE 16-row tile holding both halves of the pair (lanes
+// r < 8 read rows c0 + r, lanes r >= 8 rows c1 + r - 8; the halves swap over a lane shuffle in
+// the epilogue).  A workgroup owns `tpw` consecutive pair tiles and
 // streams their weights as ONE register ring — the next tile's first groups are in
 // flight while the current tile's last groups are consumed and its epilogue runs —
 // and stages X once per workgroup instead of once per tile.  With one workgroup per
@@ -460,7 +415,7 @@ __global__ __launch_bounds__(NW * 64) void fused_skinny_persist_kernel(FusedArgs
               v0[i] = lo ? own : oth;
               v1[i] = lo ? oth : own;
             }
-            store_pair<1, EPI>(a, c0, c1, r, g, lo, v0, v1);
+            store_half_pair<EPI>(a, c0, c1, r, g, lo, v0, v1);
           }
           acc = f32x4{0.f, 0.f, 0.f, 0.f};
           parity ^= 1;
@@ -472,11 +427,12 @@ __global__ __launch_bounds__(NW * 64) void fused_skinny_persist_kernel(FusedArgs
 }
 
 // Balanced persistent variant ("quarter pairs"): the rows are cut into quarter pairs of
-// 4 + 4 rows (half of a TW = 1 pair tile) and every workgroup streams qpw consecutive
+// 4 + 4 rows (half of a pair tile) and every workgroup streams qpw consecutive
 // quarters, two per MFMA step (lanes r & 7 < 4 hold the step's first quarter, >= 4 its
 // second; a step with one quarter leaves the upper lanes idle: no loads, no stores).
-// 8B qkv: 384 pair tiles are 1.5 per CU, so the one-tile workgroups put 262 KB on half of
-// the CUs and 131 KB on the rest; 768 quarters = 3 per CU stream 196 KB on every CU.
+// 8B qkv: 384 pair tiles are 1.5 per CU, so workgroups of whole pair tiles (a retired sweep
+// point, profiles/r3_decode/quarter_gemv.md) put 262 KB on half of the CUs and 131 KB on the
+// rest; 768 quarters = 3 per CU stream 196 KB on every CU.
 template <int NW, int U, int D, int PRO, int EPI>
 __global__ __launch_bounds__(NW * 64) void fused_skinny_quarter_kernel(FusedArgs a, int qpw, int nq) {
   extern __shared__ __attribute__((aligned(16))) uint16_t xs[];
@@ -596,13 +552,29 @@ __global__ __launch_bounds__(NW * 64) void fused_skinny_quarter_kernel(FusedArgs
   }
 }
 
+// Dynamic LDS of a launch: the staged X rows.
+size_t staged_bytes(const FusedArgs& a) { return (size_t)a.M * (a.K + 8) * 2; }
+
+// Staged X + static LDS (two reduce buffers of NW tiles, norm partials) must fit the 160 KB.
+bool lds_fits(const FusedArgs& a, int nw) {
+  return staged_bytes(a) + (size_t)2 * nw * 64 * 16 + (size_t)nw * 16 * 4 + 16 * 4 <= 160 * 1024;
+}
+
 template <int NW, int U, int D, int PRO, int EPI>
-int launch_quarter(FusedArgs a, int ntiles, hipStream_t s) {
+int launch_two_tile(FusedArgs a, int ntiles, hipStream_t s) {
   if ((a.K / 64) % (NW * U)) return -7;
-  const size_t lds = (size_t)a.M * (a.K + 8) * 2;
-  const size_t lds_static = (size_t)2 * NW * 64 * 16 + (size_t)NW * 16 * 4 + 16 * 4;
-  if (lds + lds_static > 160 * 1024) return -6;
-  // TW = 1 pair geometry (as launch_cfg)
+  if (!lds_fits(a, NW)) return -6;
+  fused_skinny_kernel<NW, U, D, PRO, EPI><<<dim3(ntiles / 2), NW * 64, staged_bytes(a), s>>>(a);
+  DGI_CHECK_LAUNCH();
+  return 0;
+}
+
+// What the persistent launchers share: the LDS budget, the geometry of the 8 + 8 row pair
+// tiles (epi 0: 16 consecutive columns, epi 1: 8 gate + 8 up, epi 2: 8 (d, d + 64) pairs) and
+// the device's CU count, which is the return value (< 0: error).
+template <int EPI>
+int prep_pairs(FusedArgs& a, int nw) {
+  if (!lds_fits(a, nw)) return -6;
   if (EPI == 0) {
     a.gstride = 16;
     a.pair_off = 8;
@@ -618,138 +590,43 @@ int launch_quarter(FusedArgs a, int ntiles, hipStream_t s) {
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
   }
-  const int nq = 2 * ntiles;
-  const int qpw = (nq + cus - 1) / cus;
-  const int nblocks = (nq + qpw - 1) / qpw;
-  fused_skinny_quarter_kernel<NW, U, D, PRO, EPI><<<dim3(nblocks), NW * 64, lds, s>>>(a, qpw, nq);
-  DGI_CHECK_LAUNCH();
-  return 0;
-}
-
-// Per-device split-K workspace (KS partial slabs + one counter per pair tile), allocated on
-// first use outside stream capture; the engine runs its decode projections on one stream.
-struct KsWorkspace {
-  float* ws = nullptr;
-  int* cnt = nullptr;
-};
-
-KsWorkspace* ks_workspace(hipStream_t s) {
-  static KsWorkspace per_dev[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  KsWorkspace& w = per_dev[dev];
-  if (w.ws) return &w;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
-  float* ws = nullptr;
-  int* cnt = nullptr;
-  if (hipMalloc(&ws, (size_t)kKsMaxTiles * kKsMax * 256 * sizeof(float)) != hipSuccess) return nullptr;
-  if (hipMalloc(&cnt, (size_t)kKsMaxTiles * sizeof(int)) != hipSuccess ||
-      hipMemset(cnt, 0, (size_t)kKsMaxTiles * sizeof(int)) != hipSuccess) {
-    hipFree(ws);
-    return nullptr;
-  }
-  w.ws = ws;
-  w.cnt = cnt;
-  return &w;
-}
-
-template <int NW, int U, int TW, int D, int PRO, int EPI, int KS = 1>
-int launch_cfg(FusedArgs a, int N, int ntiles, hipStream_t s) {
-  static_assert(KS <= kKsMax, "workspace holds kKsMax parts");
-  if constexpr (KS > 1) {
-    KsWorkspace* ks = ntiles <= kKsMaxTiles ? ks_workspace(s) : nullptr;
-    // no workspace (first call inside a capture, huge N): the same launch without the split
-    if (!ks) return launch_cfg<NW, U, TW, D * KS <= 8 ? D * KS : D, PRO, EPI, 1>(a, N, ntiles, s);
-    a.ws = ks->ws;
-    a.cnt = ks->cnt;
-  }
-  if ((a.K / KS / 64) % (NW * U)) return -7;
-  const size_t lds = (size_t)a.M * (a.K + 8) * 2;
-  // static (reduce tiles + norm partials) + staged X must fit the 160 KB of LDS
-  const size_t lds_static = (size_t)NW * TW * 64 * 16 + (size_t)NW * 16 * 4 + 16 * 4;
-  if (lds + lds_static > 160 * 1024) return -6;
-  if (TW == 1) {
-    // pairs of 8 rows: epi 0 16 consecutive columns, epi 1 8 gate + 8 up, epi 2 8 (d, d + 64) pairs
-    if (EPI == 0) {
-      a.gstride = 16;
-      a.pair_off = 8;
-    } else if (EPI == 1) {
-      a.gstride = 8;
-    } else {
-      a.tpg = 8;
-    }
-  }
-  const int nblocks = (TW == 2 ? ntiles / 2 : ntiles) * KS;
-  fused_skinny_kernel<NW, U, TW, D, PRO, EPI, KS><<<dim3(nblocks), NW * 64, lds, s>>>(a);
-  DGI_CHECK_LAUNCH();
-  (void)N;
-  return 0;
+  return cus;
 }
 
 template <int NW, int U, int D, int PRO, int EPI>
 int launch_persist(FusedArgs a, int ntiles, hipStream_t s) {
   if ((a.K / 64) % (NW * U)) return -7;
-  const size_t lds = (size_t)a.M * (a.K + 8) * 2;
-  const size_t lds_static = (size_t)2 * NW * 64 * 16 + (size_t)NW * 16 * 4 + 16 * 4;
-  if (lds + lds_static > 160 * 1024) return -6;
-  // TW = 1 pair geometry (as launch_cfg)
-  if (EPI == 0) {
-    a.gstride = 16;
-    a.pair_off = 8;
-  } else if (EPI == 1) {
-    a.gstride = 8;
-  } else {
-    a.tpg = 8;
-  }
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
+  const int cus = prep_pairs<EPI>(a, NW);
+  if (cus < 0) return cus;
   const int tpw = (ntiles + cus - 1) / cus;
   const int nblocks = (ntiles + tpw - 1) / tpw;
-  fused_skinny_persist_kernel<NW, U, D, PRO, EPI><<<dim3(nblocks), NW * 64, lds, s>>>(a, tpw, ntiles);
+  fused_skinny_persist_kernel<NW, U, D, PRO, EPI><<<dim3(nblocks), NW * 64, staged_bytes(a), s>>>(a, tpw, ntiles);
   DGI_CHECK_LAUNCH();
   return 0;
 }
 
-// cfg: (waves per workgroup, K-steps per load group, tiles per workgroup, groups in flight);
-// 12-16: persistent (waves, K-steps per group, groups in flight) with TW = 1
+template <int NW, int U, int D, int PRO, int EPI>
+int launch_quarter(FusedArgs a, int ntiles, hipStream_t s) {
+  if ((a.K / 64) % (NW * U)) return -7;
+  const int cus = prep_pairs<EPI>(a, NW);
+  if (cus < 0) return cus;
+  const int nq = 2 * ntiles;
+  const int qpw = (nq + cus - 1) / cus;
+  const int nblocks = (nq + qpw - 1) / qpw;
+  fused_skinny_quarter_kernel<NW, U, D, PRO, EPI><<<dim3(nblocks), NW * 64, staged_bytes(a), s>>>(a, qpw, nq);
+  DGI_CHECK_LAUNCH();
+  return 0;
+}
+
+// cfg -> kernel<waves per workgroup, K-steps per load group, groups in flight>; the ids are
+// those of the sweeps under profiles/ (ops.FUSED_CFGS is the same table)
 template <int PRO, int EPI>
-int launch(const FusedArgs& a, int N, int ntiles, int cfg, hipStream_t s) {
+int launch(const FusedArgs& a, int ntiles, int cfg, hipStream_t s) {
   switch (cfg) {
-    case 0: case 1: return launch_cfg<8, 2, 2, 2, PRO, EPI>(a, N, ntiles, s);
-    case 2: return launch_cfg<4, 4, 2, 2, PRO, EPI>(a, N, ntiles, s);
-    case 3: return launch_cfg<16, 1, 2, 2, PRO, EPI>(a, N, ntiles, s);
-    case 4: return launch_cfg<8, 1, 2, 2, PRO, EPI>(a, N, ntiles, s);
-    case 5: return launch_cfg<4, 2, 2, 2, PRO, EPI>(a, N, ntiles, s);
-    case 6: return launch_cfg<8, 1, 1, 4, PRO, EPI>(a, N, ntiles, s);
-    case 7: return launch_cfg<8, 1, 2, 4, PRO, EPI>(a, N, ntiles, s);
-    case 8: return launch_cfg<4, 2, 1, 4, PRO, EPI>(a, N, ntiles, s);
-    case 9: return launch_cfg<4, 2, 2, 4, PRO, EPI>(a, N, ntiles, s);
-    case 10: return launch_cfg<8, 2, 1, 2, PRO, EPI>(a, N, ntiles, s);
-    case 11: return launch_cfg<4, 1, 1, 8, PRO, EPI>(a, N, ntiles, s);
-    // persistent one-ring workgroups (TW = 1 pair tiles, ntiles of them)
+    case 7: return launch_two_tile<8, 1, 4, PRO, EPI>(a, ntiles, s);
     case 12: return launch_persist<8, 1, 8, PRO, EPI>(a, ntiles, s);
-    case 13: return launch_persist<8, 2, 4, PRO, EPI>(a, ntiles, s);
-    case 14: return launch_persist<4, 2, 8, PRO, EPI>(a, ntiles, s);
-    case 15: return launch_persist<8, 2, 6, PRO, EPI>(a, ntiles, s);
     case 16: return launch_persist<16, 1, 4, PRO, EPI>(a, ntiles, s);
-    // K split over two workgroups per pair tile (one-tile workgroups, TW = 1)
-    case 17: return launch_cfg<8, 1, 1, 4, PRO, EPI, 2>(a, N, ntiles, s);
-    case 18: return launch_cfg<4, 1, 1, 4, PRO, EPI, 2>(a, N, ntiles, s);
-    case 19: return launch_cfg<8, 2, 1, 2, PRO, EPI, 2>(a, N, ntiles, s);
-    case 20: return launch_cfg<4, 2, 1, 4, PRO, EPI, 2>(a, N, ntiles, s);
-    case 21: return launch_cfg<4, 1, 1, 8, PRO, EPI, 2>(a, N, ntiles, s);
-    // balanced persistent quarter-pair workgroups (waves, K-steps per group, groups in flight)
-    case 22: return launch_quarter<8, 1, 8, PRO, EPI>(a, ntiles, s);
-    case 23: return launch_quarter<8, 2, 4, PRO, EPI>(a, ntiles, s);
     case 24: return launch_quarter<16, 1, 4, PRO, EPI>(a, ntiles, s);
-    case 25: return launch_quarter<4, 2, 8, PRO, EPI>(a, ntiles, s);
-    case 26: return launch_quarter<8, 1, 4, PRO, EPI>(a, ntiles, s);
     default: return -5;
   }
 }
@@ -771,7 +648,7 @@ extern "C" int dgi_fused_skinny(const void* x, int ldx, const void* res, int ldr
   FusedArgs a{(const uint16_t*)x, ldx, (const uint16_t*)res, ldr, (uint16_t*)res_out, (const uint16_t*)gamma,
               eps, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, ldy, M, K, 1, 32, 16,
               positions, cos_sin, slots, (uint16_t*)k_cache, (uint16_t*)v_cache, nh, nkv, 0};
-  int ntiles;  // 16-row weight tiles of the launch (two per workgroup at TW = 2)
+  int ntiles;  // 16-row weight tiles of the launch (two per workgroup in fused_skinny_kernel)
   if (epi == 0) {
     if (N % 32) return -4;
     ntiles = N / 16;
@@ -794,7 +671,7 @@ extern "C" int dgi_fused_skinny(const void* x, int ldx, const void* res, int ldr
     return -5;
   }
   if (pro < 0 || pro > 2) return -5;
-#define DGI_FS(P, E) if (pro == P && epi == E) return launch<P, E>(a, N, ntiles, cfg, s);
+#define DGI_FS(P, E) if (pro == P && epi == E) return launch<P, E>(a, ntiles, cfg, s);
   DGI_FS(0, 0) DGI_FS(1, 0) DGI_FS(2, 0)
   DGI_FS(0, 1) DGI_FS(1, 1) DGI_FS(2, 1)
   DGI_FS(0, 2) DGI_FS(1, 2) DGI_FS(2, 2)

@@ -151,11 +151,10 @@ int dispatch(int cfg, const void* x, int ldx, const void* w, const void* bias, v
   switch (cfg) {
     case 1: return launch<16, MT, 1, 1>(x, ldx, w, bias, y, ldy, M, N, K, s);
     case 2: return launch<8, MT, 2, 2>(x, ldx, w, bias, y, ldy, M, N, K, s);
-    case 3: return launch<16, MT, 2, 1>(x, ldx, w, bias, y, ldy, M, N, K, s);
     case 4: return launch<8, MT, 1, 2>(x, ldx, w, bias, y, ldy, M, N, K, s);
-    case 5: return MT == 1 ? launch<16, 1, 4, 1>(x, ldx, w, bias, y, ldy, M, N, K, s)   // MT 2 would spill
-                           : launch<16, MT, 2, 1>(x, ldx, w, bias, y, ldy, M, N, K, s);
-    case 6: return launch<4, MT, 2, 4>(x, ldx, w, bias, y, ldy, M, N, K, s);
+    case 5:   // four column tiles per wave; two for 17..32 rows (four would spill)
+      if constexpr (MT == 1) return launch<16, 1, 4, 1>(x, ldx, w, bias, y, ldy, M, N, K, s);
+      else return launch<16, MT, 2, 1>(x, ldx, w, bias, y, ldy, M, N, K, s);
     // deeper rings: more bytes in flight per wave for short kernels (o-proj) and long K (down)
     case 7: return launch<8, MT, 1, 1, 4>(x, ldx, w, bias, y, ldy, M, N, K, s);
     case 8: return launch<8, MT, 1, 2, 4>(x, ldx, w, bias, y, ldy, M, N, K, s);
@@ -168,8 +167,8 @@ int dispatch(int cfg, const void* x, int ldx, const void* w, const void* bias, v
 
 }  // namespace
 
-// cfg selects (waves per workgroup, column tiles per wave, K-steps per group);
-// 0 = pick from the shape.  Requires K % 1024 == 0 (16 K-steps per group).
+// cfg selects (waves per workgroup, column tiles per wave, K-steps per group), the ids of
+// ops.SKINNY_CFGS (3 and 6 are retired sweep points and return -4); 0 = 4.  Requires K % 1024 == 0 (16 K-steps per group).
 extern "C" int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int M,
                                int N, int K, int cfg, hipStream_t s) {
   if (M <= 0 || N <= 0) return 0;

@@ -396,7 +396,20 @@ def _use_skinny(M: int, N: int, K: int) -> bool:
     return M <= 8 or (N <= 4096 and M <= 16) or (N >= 16384 and M <= 16)
 
 
-SKINNY_CFG = int(os.environ.get("DGI_SKINNY_CFG", "0"))    # > 0 forces a skinny_gemm launch config (sweeps)
+def _env_cfg(name: str, unset: int, table: dict) -> int:
+    """A launch-config override from the environment: ``unset`` when absent, else a key of ``table``."""
+    cfg = int(os.environ.get(name, str(unset)))
+    if cfg != unset and cfg not in table:
+        raise ValueError(f"{name}={cfg}: not a launch config of this build, choose from {sorted(table)}")
+    return cfg
+
+
+# launch configs of skinny_gemm: cfg -> (waves per workgroup, column tiles per wave, 64-deep K steps
+# per load group, ring depth); 0 runs 4.  cfg 5 runs two column tiles at M > 16.  _skinny_cfg selects
+# 4 and 5; the others are sweep points (profiles/r1_skinny_gemm.md), of which 3 and 6 are retired.
+SKINNY_CFGS = {1: (16, 1, 1, 2), 2: (8, 2, 2, 2), 4: (8, 1, 2, 2), 5: (16, 4, 1, 2),
+               7: (8, 1, 1, 4), 8: (8, 1, 2, 4), 9: (4, 1, 2, 4), 10: (4, 1, 1, 8), 11: (8, 1, 1, 8)}
+SKINNY_CFG = _env_cfg("DGI_SKINNY_CFG", 0, SKINNY_CFGS)    # > 0 forces a skinny_gemm launch config (sweeps)
 
 
 def _skinny_cfg(M: int, N: int) -> int:
@@ -507,25 +520,29 @@ def linear(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None,
 # Fused decode GEMM (fused_decode.hip): RMSNorm prologue + SwiGLU / RoPE+KV epilogue.
 # Where it pays (profiles/r2_decode8b_fused.md, hipGraph-timed, weights cold):
 # the qkv projection at M <= 8 (15 vs 18 us at M = 1 on 8B); gate_up on the persistent
-# one-ring workgroups (cfg 12-16: X staged once per CU, one weight stream per CU) at every
+# one-ring workgroups (cfg 12 and 16: X staged once per CU, one weight stream per CU) at every
 # M <= 16 (55.5 vs 62.4 us unfused at M = 16, profiles/r3_decode/persistent_gemv.md).
 # K <= 4096 (8B-class) like _use_skinny.
 # DGI_FUSED_DECODE=0 disables, =force uses it for every M <= 16 and K.
 FUSED_DECODE = os.environ.get("DGI_FUSED_DECODE", "1")
 FUSED_MAX_M = {"qkv": 8, "gate_up": 16}
-# launch config per projection and row count (fused_decode.hip cfg = waves, K-steps per load
-# group, tiles per workgroup, load ring depth: 6 = 8x1 one-tile ring 4, 7 = 8x1 two-tile ring 4,
-# 8 = 4x2 one-tile ring 4, 10 = 8x2 one-tile, 11 = 4x1 one-tile ring 8; persistent one-ring
-# workgroups 12 = 8x1 ring 8, 16 = 16x1 ring 4; balanced quarter-pair workgroups 24 = 16x1 ring 4).  Fastest per M on the 8B shapes, weights cold,
-# hipGraph-timed (profiles/r3_decode_gemm/README.md, profiles/r3_decode/persistent_gemv.md): qkv
-# 16.6 -> 15.0 us at M = 1 against round 2's fixed config 4; gate_up + SwiGLU 48.6 -> 43.0 us at
-# M = 1, 56.2 -> 45.5 at M = 4, 66.1 -> 48.2 at M = 8 (cfg 16; 16 waves do not fit M = 16's LDS).
-# qkv + RoPE/KV at M <= 8: balanced quarter-pair workgroups, 16 waves (cfg 24: 384 pair tiles
-# = 768 quarters, 3 per CU instead of 1.5 whole tiles): 14.96 -> 13.16 us at M = 1, 18.52 -> 17.40
-# at M = 4, 21.37 -> 20.23 at M = 8 (profiles/r3_decode/quarter_gemv.md).
+# launch configs of fused_skinny: cfg -> (kernel kind, waves per workgroup, 64-deep K steps per
+# load group, ring depth).  "two_tile": one workgroup per pair of 16-row tiles; "persistent": one
+# workgroup per CU streams 8 + 8 row pair tiles through one ring and stages X once; "quarter": the
+# same on 4 + 4 row quarter pairs, which balances 1.5 pair tiles per CU.  The ids are those of the
+# sweeps (profiles/r3_decode_gemm/README.md, profiles/r3_decode/persistent_gemv.md, quarter_gemv.md,
+# profiles/r5_decode/README.md), whose other points are retired.
+FUSED_CFGS = {7: ("two_tile", 8, 1, 4), 12: ("persistent", 8, 1, 8), 16: ("persistent", 16, 1, 4),
+              24: ("quarter", 16, 1, 4)}
+# Config per projection and row count, the fastest on the 8B shapes, weights cold, hipGraph-timed.
+# gate_up + SwiGLU: cfg 16 up to M = 8 (43.0 us at M = 1, 45.5 at 4, 48.2 at 8 against 48.6 / 56.2 /
+# 66.1 for the two-tile workgroups), cfg 12 above (16 waves do not fit M = 16's LDS).  qkv + RoPE/KV:
+# cfg 24 up to M = 8 (13.16 us at M = 1, 17.40 at 4, 20.23 at 8 against 14.96 / 18.52 / 21.37 for the
+# retired one-pair-tile workgroups, profiles/r3_decode/quarter_gemv.md); cfg 7 above, which only DGI_FUSED_DECODE=force reaches (FUSED_MAX_M).
 FUSED_M_CFG = {"qkv": ((8, 24), (16, 7)), "gate_up": ((8, 16), (16, 12))}
-FUSED_KIND_CFG = {"qkv": int(os.environ.get("DGI_FUSED_QKV_CFG", "-1")),
-                  "gate_up": int(os.environ.get("DGI_FUSED_GU_CFG", "-1"))}
+FUSED_KIND_CFG = {"qkv": _env_cfg("DGI_FUSED_QKV_CFG", -1, FUSED_CFGS),
+                  "gate_up": _env_cfg("DGI_FUSED_GU_CFG", -1, FUSED_CFGS)}
+FUSED_CFG = _env_cfg("DGI_FUSED_CFG", -1, FUSED_CFGS)      # >= 0 overrides FUSED_KIND_CFG
 
 
 def fused_cfg(kind: str, M: int) -> int:
@@ -567,9 +584,6 @@ def fused_skinny_ref(y, x, res, res_out, gamma, eps, w, bias, pro, epi, position
     return y
 
 
-FUSED_CFG = int(os.environ.get("DGI_FUSED_CFG", "-1"))      # >= 0 overrides FUSED_KIND_CFG
-
-
 def fused_skinny(y, x, res, res_out, gamma, eps, w, bias, pro: int, epi: int, positions=None, cos_sin=None,
                  slots=None, k_cache=None, v_cache=None, nh: int = 0, nkv: int = 0, cfg: Optional[int] = None):
     """y = epi(rmsnorm_pro(x [+ res]) @ w.T + bias); pro 2 also writes res_out = x + res.
@@ -587,10 +601,11 @@ def fused_skinny(y, x, res, res_out, gamma, eps, w, bias, pro: int, epi: int, po
                             k_cache, v_cache, nh, nkv)
 
 
-# batch-1 decode o-proj (no prologue / epilogue) through the persistent fused GEMV config 16:
+# batch-1 decode o-proj (no prologue / epilogue) through the persistent fused GEMV, 16 waves:
 # 8.35 vs 8.80 us for the skinny kernel on Llama-3-8B (profiles/r4_decode/plain_proj_fused_configs.json);
 # at M >= 2 the skinny kernel is as fast or faster.  DGI_OPROJ_FUSED=0: always ops.linear
 OPROJ_FUSED = os.environ.get("DGI_OPROJ_FUSED", "1") == "1"
+OPROJ_CFG = 16
 
 
 def decode_proj(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -601,8 +616,7 @@ def decode_proj(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
             and w.dtype == torch.bfloat16 and w.is_contiguous() and w.shape[1] == K
             and fused_decode_ok(M, K, "qkv") and w.shape[0] % 16 == 0):
         y = torch.empty(M, w.shape[0], dtype=x.dtype, device=x.device)
-        _call("fused_skinny", y, x, None, None, None, 0.0, w, None, 0, 0, None, None, None, None, None, 0, 0, 16)
-        return y
+        return fused_skinny(y, x, None, None, None, 0.0, w, None, pro=0, epi=0, cfg=OPROJ_CFG)
     return linear(x, w)
 
 

@@ -4,7 +4,7 @@ GEMV (no prologue, plain store) per launch config vs hipBLASLt, hipGraph-timed w
 weights streamed cold (rotated over buffers larger than the MALL).  Prints one JSON
 line per M with us per launch and the max error vs the fp32 reference.
 
-    python scripts/down_gemv_bench.py [--ms 1 2 4 8 16] [--cfgs 6 7 8 10 11 12 13 14 15 16]
+    python scripts/down_gemv_bench.py [--ms 1 2 4 8 16] [--cfgs 7 12 16 24]
 """
 import argparse
 import json
@@ -22,7 +22,7 @@ from fused_decode_bench import graph_time  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ms", type=int, nargs="+", default=[1, 2, 4, 8, 16])
-    ap.add_argument("--cfgs", type=int, nargs="+", default=[6, 7, 8, 10, 11, 12, 13, 14, 15, 16])
+    ap.add_argument("--cfgs", type=int, nargs="+", default=sorted(ops.FUSED_CFGS))
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--k", type=int, default=14336)
     a = ap.parse_args()

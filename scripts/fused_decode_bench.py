@@ -114,7 +114,7 @@ def bench_plain(shapes, Ms):
             y = torch.empty(M, N, device=dev, dtype=bf)
             row = {"gemm": name, "M": M, "N": N, "K": K,
                    "hipblaslt": round(graph_time(lambda i: torch.matmul(x, ws[i % nbuf].t(), out=y)), 2)}
-            for cfg in range(1, 12):
+            for cfg in sorted(ops.SKINNY_CFGS):
                 try:
                     row[f"skinny_c{cfg}"] = round(graph_time(
                         lambda i: torch.ops.dgi.skinny_gemm(y, x, ws[i % nbuf], None, cfg)), 2)
@@ -187,7 +187,7 @@ def bench_plain_fused(shapes, Ms, cfgs):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--cfgs", type=int, nargs="+", default=[0, 2, 3, 4, 5])
+    ap.add_argument("--cfgs", type=int, nargs="+", default=sorted(ops.FUSED_CFGS))
     ap.add_argument("--skip-attn", action="store_true")
     ap.add_argument("--skip-gemms", action="store_true", help="skip the fused qkv / gate_up table")
     ap.add_argument("--plain-fused", action="store_true", help="also o-proj / down through fused_skinny configs")

@@ -62,7 +62,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ms", type=int, nargs="+", default=[1, 2, 4, 8, 16, 32])
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES))
-    ap.add_argument("--cfg", type=int, nargs="+", default=[0])
+    ap.add_argument("--cfg", type=int, nargs="+", default=[0], choices=[0, *sorted(ops.SKINNY_CFGS)])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--fp8-cfg", type=int, nargs="*", default=[0], help="skinny_gemm_w8 launch configs (none: skip)")
     ap.add_argument("--no-hipblaslt", action="store_true")

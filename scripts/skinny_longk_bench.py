@@ -19,7 +19,7 @@ from fused_decode_bench import graph_time  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ms", type=int, nargs="+", default=[1, 4])
-    ap.add_argument("--cfgs", type=int, nargs="+", default=list(range(1, 12)))
+    ap.add_argument("--cfgs", type=int, nargs="+", default=sorted(ops.SKINNY_CFGS))
     a = ap.parse_args()
     ops.load_native(required=True)
     dev, bf = "cuda", torch.bfloat16

@@ -418,3 +418,30 @@ def test_trimmed_last_layer_is_bit_identical_on_a_mixed_step(monkeypatch):
             assert ("_trimmed_tail" in seen) == flag
             assert ("_forward_layers_quant" in seen) == (weight_quant is not None)
         assert logits[True].shape[0] == 2 and torch.equal(logits[True], logits[False])
+
+
+@pytest.mark.parametrize("name,unset,table", [("DGI_FUSED_CFG", -1, "FUSED_CFGS"), ("DGI_FUSED_QKV_CFG", -1, "FUSED_CFGS"),
+                                              ("DGI_FUSED_GU_CFG", -1, "FUSED_CFGS"), ("DGI_SKINNY_CFG", 0, "SKINNY_CFGS")])
+def test_launch_config_override_outside_the_table_raises(monkeypatch, name, unset, table):
+    """The overrides read at import accept the ids of their table and the unset value; a retired id
+    (3 was a config of both kernels) raises and names the variable."""
+    table = getattr(ops, table)
+    monkeypatch.delenv(name, raising=False)
+    assert ops._env_cfg(name, unset, table) == unset
+    for cfg in table:
+        monkeypatch.setenv(name, str(cfg))
+        assert ops._env_cfg(name, unset, table) == cfg
+    monkeypatch.setenv(name, "3")
+    with pytest.raises(ValueError, match=name):
+        ops._env_cfg(name, unset, table)
+
+
+def test_fused_cfg_selects_only_compiled_configs(monkeypatch):
+    monkeypatch.setattr(ops, "FUSED_CFG", -1)
+    monkeypatch.setattr(ops, "FUSED_KIND_CFG", {"qkv": -1, "gate_up": -1})
+    for kind in ("qkv", "gate_up"):
+        for M in range(1, 17):
+            assert ops.fused_cfg(kind, M) in ops.FUSED_CFGS
+    assert ops.OPROJ_CFG in ops.FUSED_CFGS and not {3, 6} & set(ops.SKINNY_CFGS)
+    assert all(ops._skinny_cfg(M, N) in (0, *ops.SKINNY_CFGS) for M in range(1, 33) for N in (4096, 28672))
+

@@ -16,16 +16,18 @@ int dgi_fused_add_rmsnorm(void* x, void* residual, const void* w, int T, int H, 
                           hipStream_t s);
 int dgi_rope_cache(void* qkv, int T, int qkv_stride, const int* positions, const float* cos_sin,
                    int nh, int nkv, int hd, int rd, int mode, const int* slot_mapping, void* k_cache,
-                   void* v_cache, int block_size, hipStream_t s);
+                   void* v_cache, int block_size, const float* kv_inv_scale, hipStream_t s);
 int dgi_paged_decode(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                      const int* block_tables, int bt_stride, const int* context_lens, void* out,
                      int out_stride, float* part_o, float* part_lse, int* counters, int B, int nh, int nkv,
-                     int hd, int block_size, int max_splits, int part_size, float scale, hipStream_t s);
+                     int hd, int block_size, int max_splits, int part_size, float scale, const float* kv_scale,
+                     hipStream_t s);
 int dgi_paged_prefill(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                       const int* block_tables, int bt_stride, const int* cu_seqlens_q,
                       const int* context_lens, const int* tiles, int n_tiles, void* out,
                       int out_stride, int nh, int nkv, int hd, int block_size, float scale,
-                      const unsigned long long* tree_mask, int tree_n, int tile_rows, hipStream_t s);
+                      const unsigned long long* tree_mask, int tree_n, int tile_rows, const float* kv_scale,
+                      hipStream_t s);
 int dgi_silu_mul(const void* gu, void* out, int T, int I, hipStream_t s);
 int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int M,
                     int N, int K, int nw, hipStream_t s);
@@ -92,6 +94,25 @@ void check_i32(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
+// A paged K or V cache and its scales: bf16 pages take no scales; e4m3 pages (float8_e4m3fn) take
+// one fp32 [2, nkv] tensor (row 0 for K, row 1 for V).  Returns the scale pointer, or nullptr for bf16.
+const float* check_kv(const at::Tensor& k_cache, const at::Tensor& v_cache, const c10::optional<at::Tensor>& scale,
+                      int64_t nkv, const char* what) {
+  check_dev(k_cache, "k_cache"); check_dev(v_cache, "v_cache");
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(), what, ": k_cache and v_cache differ in dtype");
+  if (k_cache.scalar_type() == at::kBFloat16) {
+    TORCH_CHECK(!(scale.has_value() && scale->defined()), what, ": scales given for a bfloat16 KV cache");
+    return nullptr;
+  }
+  TORCH_CHECK(k_cache.scalar_type() == at::kFloat8_e4m3fn, what, ": the KV cache must be bfloat16 or float8_e4m3fn");
+  TORCH_CHECK(scale.has_value() && scale->defined(), what, ": a float8_e4m3fn KV cache needs its [2, nkv] scales");
+  check_dev(*scale, "kv scale");
+  TORCH_CHECK(scale->scalar_type() == at::kFloat && scale->is_contiguous() && scale->dim() == 2 &&
+                  scale->size(0) == 2 && scale->size(1) == nkv,
+              what, ": kv scales must be a contiguous fp32 [2, nkv] tensor");
+  return scale->data_ptr<float>();
+}
+
 // int32 [rows, width] whose rows are dense but may lie further apart than their width (a column
 // slice of a wider persistent table): the kernels take the row stride
 void check_i32_rows(const at::Tensor& t, const char* name) {
@@ -126,9 +147,9 @@ void fused_add_rmsnorm(at::Tensor x, at::Tensor residual, const at::Tensor& w, d
 // mode 0 = NeoX pairing, 1 = interleaved (GPT-J / GLM)
 void rope_cache(at::Tensor qkv, const at::Tensor& positions, const at::Tensor& cos_sin, int64_t nh,
                 int64_t nkv, int64_t hd, const at::Tensor& slot_mapping, at::Tensor k_cache,
-                at::Tensor v_cache, int64_t mode) {
+                at::Tensor v_cache, int64_t mode, const c10::optional<at::Tensor>& kv_inv_scale) {
   check_bf16(qkv, "qkv"); check_i32(positions, "positions"); check_i32(slot_mapping, "slot_mapping");
-  check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
+  const float* inv = check_kv(k_cache, v_cache, kv_inv_scale, nkv, "rope_cache");
   TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous() && cos_sin.size(1) <= hd);
   TORCH_CHECK(positions.numel() == 0 || cos_sin.dim() == 2);
   TORCH_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1 && qkv.size(1) >= (nh + 2 * nkv) * hd);
@@ -139,7 +160,7 @@ void rope_cache(at::Tensor qkv, const at::Tensor& positions, const at::Tensor& c
   check_rc(dgi_rope_cache(qkv.data_ptr(), T, (int)qkv.stride(0), positions.data_ptr<int>(),
                           cos_sin.data_ptr<float>(), (int)nh, (int)nkv, (int)hd, (int)cos_sin.size(1),
                           (int)mode, slot_mapping.data_ptr<int>(), k_cache.data_ptr(), v_cache.data_ptr(),
-                          (int)k_cache.size(2), cur_stream()),
+                          (int)k_cache.size(2), inv, cur_stream()),
            "rope_cache");
 }
 
@@ -148,8 +169,9 @@ void paged_decode(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cache
                   const at::Tensor& v_cache, const at::Tensor& block_tables,
                   const at::Tensor& context_lens, at::Tensor part_o, at::Tensor part_lse,
                   int64_t nh, int64_t nkv, int64_t max_splits, int64_t part_size, double scale,
-                  const c10::optional<at::Tensor>& counters) {
-  check_bf16(out, "out"); check_bf16(q, "q"); check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
+                  const c10::optional<at::Tensor>& counters, const c10::optional<at::Tensor>& kv_scale) {
+  check_bf16(out, "out"); check_bf16(q, "q");
+  const float* ksc = check_kv(k_cache, v_cache, kv_scale, nkv, "paged_decode");
   check_i32_rows(block_tables, "block_tables"); check_i32(context_lens, "context_lens");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1 && out.dim() == 2 && out.stride(1) == 1);
   const int hd = (int)k_cache.size(3);
@@ -174,7 +196,7 @@ void paged_decode(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cache
                             max_splits > 1 ? part_o.data_ptr<float>() : nullptr,
                             max_splits > 1 ? part_lse.data_ptr<float>() : nullptr, cnt, B, (int)nh,
                             (int)nkv, hd, (int)k_cache.size(2), (int)max_splits, (int)part_size,
-                            (float)scale, cur_stream()),
+                            (float)scale, ksc, cur_stream()),
            "paged_decode");
 }
 
@@ -182,8 +204,10 @@ void paged_prefill(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cach
                    const at::Tensor& v_cache, const at::Tensor& block_tables,
                    const at::Tensor& cu_seqlens_q, const at::Tensor& context_lens,
                    const at::Tensor& tiles, int64_t nh, int64_t nkv, double scale,
-                   const c10::optional<at::Tensor>& tree_mask, int64_t tree_n, int64_t tile_rows) {
-  check_bf16(out, "out"); check_bf16(q, "q"); check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
+                   const c10::optional<at::Tensor>& tree_mask, int64_t tree_n, int64_t tile_rows,
+                   const c10::optional<at::Tensor>& kv_scale) {
+  check_bf16(out, "out"); check_bf16(q, "q");
+  const float* ksc = check_kv(k_cache, v_cache, kv_scale, nkv, "paged_prefill");
   check_i32_rows(block_tables, "block_tables"); check_i32(cu_seqlens_q, "cu_seqlens_q");
   check_i32(context_lens, "context_lens"); check_i32(tiles, "tiles");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1 && out.dim() == 2 && out.stride(1) == 1);
@@ -202,7 +226,7 @@ void paged_prefill(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cach
                              cu_seqlens_q.data_ptr<int>(), context_lens.data_ptr<int>(),
                              tiles.data_ptr<int>(), (int)tiles.size(0), out.data_ptr(),
                              (int)out.stride(0), (int)nh, (int)nkv, hd, (int)k_cache.size(2),
-                             (float)scale, tm, (int)tree_n, (int)tile_rows, cur_stream()),
+                             (float)scale, tm, (int)tree_n, (int)tile_rows, ksc, cur_stream()),
            "paged_prefill");
 }
 
@@ -639,13 +663,13 @@ TORCH_LIBRARY(dgi, m) {
   m.def("rmsnorm(Tensor(a!) out, Tensor x, Tensor w, float eps) -> ()");
   m.def("fused_add_rmsnorm(Tensor(a!) x, Tensor(b!) residual, Tensor w, float eps) -> ()");
   m.def("rope_cache(Tensor(a!) qkv, Tensor positions, Tensor cos_sin, int nh, int nkv, int hd, "
-        "Tensor slot_mapping, Tensor(b!) k_cache, Tensor(c!) v_cache, int mode=0) -> ()");
+        "Tensor slot_mapping, Tensor(b!) k_cache, Tensor(c!) v_cache, int mode=0, Tensor? kv_inv_scale=None) -> ()");
   m.def("paged_decode(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor context_lens, Tensor(b!) part_o, Tensor(c!) part_lse, int nh, int nkv, int max_splits, "
-        "int part_size, float scale, Tensor(d!)? counters=None) -> ()");
+        "int part_size, float scale, Tensor(d!)? counters=None, Tensor? kv_scale=None) -> ()");
   m.def("paged_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor cu_seqlens_q, Tensor context_lens, Tensor tiles, int nh, int nkv, float scale, "
-        "Tensor? tree_mask, int tree_n, int tile_rows=128) -> ()");
+        "Tensor? tree_mask, int tree_n, int tile_rows=128, Tensor? kv_scale=None) -> ()");
   m.def("silu_mul(Tensor(a!) out, Tensor gu) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
   m.def("skinny_gemm_w8(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");

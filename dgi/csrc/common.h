@@ -61,6 +61,51 @@ __device__ __forceinline__ bf16x8 as_bf16x8(const u32x4& v) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// ---- e4m3 (OCP float8_e4m3fn) helpers: W8A16 weights and the fp8 KV cache.
+// Two e4m3 codes of `word` (low or high half) -> two bf16 in one word.
+__device__ __forceinline__ uint32_t widen2(uint32_t word, bool hi) {
+  const f32x2v f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)word, true)
+                      : __builtin_amdgcn_cvt_pk_f32_fp8((int)word, false);
+  // upper halves of the two words, f[0] low (v_perm_b32: selector bytes 0-3 index the second
+  // source, 4-7 the first); exact: an e4m3 value has 3 mantissa bits, bf16 keeps 7
+  return __builtin_amdgcn_perm(__float_as_uint(f[1]), __float_as_uint(f[0]), 0x07060302u);
+}
+
+// 8 e4m3 (two words) -> 8 bf16 (one MFMA operand / one 16-byte LDS chunk)
+__device__ __forceinline__ u32x4 widen8_u32(uint32_t a, uint32_t b) {
+  u32x4 r;
+  r[0] = widen2(a, false);
+  r[1] = widen2(a, true);
+  r[2] = widen2(b, false);
+  r[3] = widen2(b, true);
+  return r;
+}
+
+__device__ __forceinline__ bf16x8 widen8(uint32_t a, uint32_t b) { return as_bf16x8(widen8_u32(a, b)); }
+
+// KV-cache quantiser: code = rne_e4m3(clamp(x * inv_scale, -448, 448)) for 8 values.  The clamp
+// is explicit (selects, so a NaN stays a NaN): the conversion's own overflow mode never matters.
+__device__ __forceinline__ uint2 quant8_e4m3(const float* x, float inv_scale) {
+  float c[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float v = x[j] * inv_scale;
+    v = v > 448.f ? 448.f : v;
+    v = v < -448.f ? -448.f : v;
+    c[j] = v;
+  }
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[4], c[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[6], c[7], hi, true);
+  return uint2{(uint32_t)lo, (uint32_t)hi};
+}
+
+// The optional trailing kernel argument of the fp8-KV instantiations (a parameter pack that is
+// empty for bf16, so the bf16 kernels keep their argument list).
+__device__ __forceinline__ const float* pack_ptr(const float* p) { return p; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

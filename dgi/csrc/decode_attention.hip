@@ -25,6 +25,8 @@
 //   in the same launch (ticket counters in the workspace: write-through
 //   partials, one relaxed ticket, one acquire on the last arriver) or a small
 //   reduce kernel does.
+#include <type_traits>
+
 #include "common.h"
 
 using namespace dgi;
@@ -53,13 +55,19 @@ constexpr int decode_wave_lds() {
   return (32 * HD * 2 > 16 * (HD + 4) * 4 ? 32 * HD * 2 : 16 * (HD + 4) * 4) + 128;
 }
 
-template <int HD, int NW>
+// FP8: the caches hold e4m3 codes (one byte per element, same page layout).  Only the load stage
+// differs: a lane fetches the 8 codes of each K fragment / V chunk with one 8-byte load and widens
+// them to bf16 in registers (exact) right before the MFMA / the LDS write, so the LDS image, the
+// transposed reads, the MFMA sequence, the softmax and the split reduce are the bf16 kernel's.
+// The trailing argument is kv_scale [2, nkv] fp32: the workgroup's K scale multiplies the softmax
+// scale and its V scale the final normalisation.
+template <int HD, int NW, bool FP8, typename... S>
 __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
     const uint16_t* __restrict__ q, int q_stride, const uint16_t* __restrict__ k_cache,
     const uint16_t* __restrict__ v_cache, const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ context_lens, uint16_t* __restrict__ out, int out_stride,
     float* __restrict__ part_o, float* __restrict__ part_lse, int* __restrict__ counters, int max_splits, int nh,
-    int nkv, int bs_log2, int part_size, float scale_log2, bool page16) {
+    int nkv, int bs_log2, int part_size, float scale_log2, bool page16, S... kv_scale) {
   constexpr int KS = HD / 32;   // k-steps of the QK^T product
   constexpr int NC = HD / 16;   // 16-wide dim blocks of the PV product
   constexpr int VCH = HD / 8;   // 16-byte chunks per V row
@@ -76,6 +84,14 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
   const int h = blockIdx.y;
   const int b = blockIdx.z;
   const int ctx = context_lens[b];
+  [[maybe_unused]] float v_scale = 1.f;
+  if constexpr (FP8) {
+    const float* sc = pack_ptr(kv_scale...);
+    scale_log2 *= sc[h];
+    v_scale = sc[nkv + h];
+  }
+  [[maybe_unused]] const uint8_t* k8 = reinterpret_cast<const uint8_t*>(k_cache);
+  [[maybe_unused]] const uint8_t* v8 = reinterpret_cast<const uint8_t*>(v_cache);
   // write-through views of the split workspace (fused reduce); byte ranges cover the launch
   const __amdgpu_buffer_rsrc_t po_rs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)part_o, 0, (int)min((size_t)gridDim.z * nh * max_splits * HD * 4, (size_t)0x7fffffff), kRsrcWord3);
@@ -135,8 +151,10 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
   const int ntiles = (end - start + 31) >> 5;
   for (int t = w; t < ntiles; t += NW) {
     const int tb = start + (t << 5);
-    u32x4 kf[2][KS];
-    u32x4 vr[VCH / 2];
+    // bf16: 16-byte loads are the operands; fp8: 8-byte loads of 8 codes, widened at their use
+    using raw_t = typename std::conditional<FP8, uint2, u32x4>::type;
+    raw_t kf[2][KS];
+    raw_t vr[VCH / 2];
     if (page16 && tb + 32 <= end) {
       // full tile of 16-token pages (the engine's page size): its two pages come from two
       // scalar block-table reads, every lane's offset inside a page is a constant, so each
@@ -155,14 +173,21 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int s = 0; s < KS; ++s)
-          kf[u][s] = *reinterpret_cast<const u32x4*>(kp[u] + qi * HD + 32 * s + 8 * g);
+        for (int s = 0; s < KS; ++s) {
+          if constexpr (FP8)
+            kf[u][s] = *reinterpret_cast<const uint2*>(k8 + (kp[u] - k_cache) + qi * HD + 32 * s + 8 * g);
+          else
+            kf[u][s] = *reinterpret_cast<const u32x4*>(kp[u] + qi * HD + 32 * s + 8 * g);
+        }
       // ---- V tile -> registers (row 4k + lane / VCH of the tile; rows 16-31 on the second page)
 #pragma unroll
       for (int k = 0; k < VCH / 2; ++k) {
         const int idx = k * 64 + lane;
         const int row = idx / VCH;
-        vr[k] = *reinterpret_cast<const u32x4*>(vp[row >> 4] + (row & 15) * HD + (idx % VCH) * 8);
+        if constexpr (FP8)
+          vr[k] = *reinterpret_cast<const uint2*>(v8 + (vp[row >> 4] - v_cache) + (row & 15) * HD + (idx % VCH) * 8);
+        else
+          vr[k] = *reinterpret_cast<const u32x4*>(vp[row >> 4] + (row & 15) * HD + (idx % VCH) * 8);
       }
     } else {
       // ---- K fragments straight to VGPRs (A operand: row = token, k = dims)
@@ -173,7 +198,10 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
         const int blk = bt[tok >> bs_log2];
         const uint16_t* kpl = k_cache + ((size_t)blk * nkv + h) * head_stride + (size_t)(tok & (bs - 1)) * HD;
 #pragma unroll
-        for (int s = 0; s < KS; ++s) kf[u][s] = *reinterpret_cast<const u32x4*>(kpl + 32 * s + 8 * g);
+        for (int s = 0; s < KS; ++s) {
+          if constexpr (FP8) kf[u][s] = *reinterpret_cast<const uint2*>(k8 + (kpl - k_cache) + 32 * s + 8 * g);
+          else kf[u][s] = *reinterpret_cast<const u32x4*>(kpl + 32 * s + 8 * g);
+        }
       }
       // ---- V tile -> registers -> swizzled LDS
 #pragma unroll
@@ -185,7 +213,8 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
         int tok = min(tb + row, end - 1);
         const int blk = bt[tok >> bs_log2];
         const uint16_t* vpl = v_cache + ((size_t)blk * nkv + h) * head_stride + (size_t)(tok & (bs - 1)) * HD;
-        vr[k] = *reinterpret_cast<const u32x4*>(vpl + ch * 8);
+        if constexpr (FP8) vr[k] = *reinterpret_cast<const uint2*>(v8 + (vpl - v_cache) + ch * 8);
+        else vr[k] = *reinterpret_cast<const u32x4*>(vpl + ch * 8);
       }
     }
     if (LATE_Q && t == w) load_q();
@@ -195,8 +224,13 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
     for (int u = 0; u < 2; ++u) {
       sacc[u] = f32x4{0, 0, 0, 0};
 #pragma unroll
-      for (int s = 0; s < KS; ++s)
-        sacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(kf[u][s]), as_bf16x8(qf[s]), sacc[u], 0, 0, 0);
+      for (int s = 0; s < KS; ++s) {
+        if constexpr (FP8)
+          sacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(widen8(kf[u][s].x, kf[u][s].y), as_bf16x8(qf[s]),
+                                                            sacc[u], 0, 0, 0);
+        else
+          sacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(kf[u][s]), as_bf16x8(qf[s]), sacc[u], 0, 0, 0);
+      }
     }
     // write V (the previous tile's transposed reads are complete: in-order LDS per wave)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -205,7 +239,8 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
       const int idx = k * 64 + lane;
       const int row = idx / VCH;
       const int ch = idx % VCH;
-      *reinterpret_cast<u32x4*>(vt + v_lds_off<HD>(row, ch * 8)) = vr[k];
+      if constexpr (FP8) *reinterpret_cast<u32x4*>(vt + v_lds_off<HD>(row, ch * 8)) = widen8_u32(vr[k].x, vr[k].y);
+      else *reinterpret_cast<u32x4*>(vt + v_lds_off<HD>(row, ch * 8)) = vr[k];
     }
     // ---- online softmax (lane owns query qi; tokens 16u + 4g + i); only the sequence's last
     // tile has tokens past its end to mask
@@ -306,7 +341,8 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
       acc += reinterpret_cast<float*>(smem + ww * WREG)[qq * OROW + (d ^ o_swz(qq))] * sc;
     }
     const int head = h * G + qq;
-    const float r = acc / L;
+    float r = acc / L;
+    if constexpr (FP8) r *= v_scale;
     if (nsplit == 1) {
       out[(size_t)b * out_stride + head * HD + d] = f32_to_bf16(r);
     } else if (counters != nullptr) {
@@ -397,7 +433,8 @@ extern "C" int dgi_paged_decode(const void* q, int q_stride, const void* k_cache
                                 const void* v_cache, const int* block_tables, int bt_stride,
                                 const int* context_lens, void* out, int out_stride, float* part_o,
                                 float* part_lse, int* counters, int B, int nh, int nkv, int hd, int block_size,
-                                int max_splits, int part_size, float scale, hipStream_t s) {
+                                int max_splits, int part_size, float scale, const float* kv_scale,
+                                hipStream_t s) {
   if (B == 0) return 0;
   if (nh % nkv || nh / nkv > 16) return -2;
   // fixed parts: multiples of 128 tokens; dynamic (part_size <= 0): minimum part a multiple of 32
@@ -419,18 +456,23 @@ extern "C" int dgi_paged_decode(const void* q, int q_stride, const void* k_cache
   // few workgroups (small batch, one split: every (sequence, kv head) walks its whole
   // context): 8 waves per workgroup halve the serial tile chain of each wave
   const bool wide = max_splits == 1 && B * nkv <= 128;
+  // kv_scale != nullptr: the caches hold e4m3 codes
+#define DGI_DECODE(HDV, NWV)                                                                               \
+  do {                                                                                                     \
+    if (kv_scale)                                                                                          \
+      paged_decode_kernel<HDV, NWV, true, const float*><<<grid, 64 * NWV, NWV * decode_wave_lds<HDV>(), s>>>( \
+          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
+          bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse, counters, max_splits, nh,  \
+          nkv, bs_log2, part_size, scale_log2, page16, kv_scale);                                           \
+    else                                                                                                   \
+      paged_decode_kernel<HDV, NWV, false><<<grid, 64 * NWV, NWV * decode_wave_lds<HDV>(), s>>>(            \
+          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
+          bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse, counters, max_splits, nh,  \
+          nkv, bs_log2, part_size, scale_log2, page16);                                                     \
+  } while (0)
   if (hd == 128) {
-    if (wide) {
-      paged_decode_kernel<128, 8><<<grid, 512, 8 * decode_wave_lds<128>(), s>>>(
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,
-          block_tables, bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse,
-          counters, max_splits, nh, nkv, bs_log2, part_size, scale_log2, page16);
-    } else {
-      paged_decode_kernel<128, 4><<<grid, 256, 4 * decode_wave_lds<128>(), s>>>(
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,
-          block_tables, bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse,
-          counters, max_splits, nh, nkv, bs_log2, part_size, scale_log2, page16);
-    }
+    if (wide) DGI_DECODE(128, 8);
+    else DGI_DECODE(128, 4);
     DGI_CHECK_LAUNCH();
     if (max_splits > 1 && counters == nullptr) {
       decode_reduce_kernel<128><<<dim3(B, nh), 128, 0, s>>>(part_o, part_lse, context_lens,
@@ -439,17 +481,8 @@ extern "C" int dgi_paged_decode(const void* q, int q_stride, const void* k_cache
       DGI_CHECK_LAUNCH();
     }
   } else if (hd == 64) {
-    if (wide) {
-      paged_decode_kernel<64, 8><<<grid, 512, 8 * decode_wave_lds<64>(), s>>>(
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,
-          block_tables, bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse,
-          counters, max_splits, nh, nkv, bs_log2, part_size, scale_log2, page16);
-    } else {
-      paged_decode_kernel<64, 4><<<grid, 256, 4 * decode_wave_lds<64>(), s>>>(
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,
-          block_tables, bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse,
-          counters, max_splits, nh, nkv, bs_log2, part_size, scale_log2, page16);
-    }
+    if (wide) DGI_DECODE(64, 8);
+    else DGI_DECODE(64, 4);
     DGI_CHECK_LAUNCH();
     if (max_splits > 1 && counters == nullptr) {
       decode_reduce_kernel<64><<<dim3(B, nh), 64, 0, s>>>(part_o, part_lse, context_lens,
@@ -460,5 +493,6 @@ extern "C" int dgi_paged_decode(const void* q, int q_stride, const void* k_cache
   } else {
     return -5;
   }
+#undef DGI_DECODE
   return 0;
 }

@@ -22,6 +22,8 @@
 //   Optional tree mask: for EAGLE verification the last `tree_n` queries of a
 //   sequence see the cached prefix plus their ancestors, given as one 64-bit
 //   ancestor mask per query (built by tree.hip).
+#include <type_traits>
+
 #include "common.h"
 
 using namespace dgi;
@@ -55,19 +57,33 @@ constexpr int KT = 64;  // keys per tile
 // global loads are issued, then tile i is consumed — one barrier per 64 keys instead of
 // two, and a wave's LDS write no longer waits for every other wave before its MFMAs
 // (round 5: 24 % MFMA busy with DB = 0, profiles/r5_pmc/).
-template <int HD, int NW, int DB>
+// FP8: the caches hold e4m3 codes (one byte per element, same page layout).  load_tile /
+// load_tile_fast fetch 8 codes per chunk with 8-byte loads and store_tile widens them to bf16
+// (exact) before the LDS stores; everything after the LDS image is the bf16 kernel's.  The
+// trailing argument is kv_scale [2, nkv] fp32: the head's K scale multiplies the softmax scale,
+// its V scale the final normalisation.
+template <int HD, int NW, int DB, bool FP8, typename... S>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
     const uint16_t* __restrict__ q, int q_stride, const uint16_t* __restrict__ k_cache,
     const uint16_t* __restrict__ v_cache, const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ cu_seqlens_q, const int* __restrict__ context_lens,
     const int* __restrict__ tiles, uint16_t* __restrict__ out, int out_stride, int nh, int nkv,
-    int bs_log2, float scale_log2, const unsigned long long* __restrict__ tree_mask, int tree_n) {
+    int bs_log2, float scale_log2, const unsigned long long* __restrict__ tree_mask, int tree_n,
+    S... kv_scale) {
   __shared__ __attribute__((aligned(16))) uint16_t lds[(DB ? 2 : 1) * 2 * KT * HD];
 
   const int b = tiles[2 * blockIdx.x];
   const int t0 = tiles[2 * blockIdx.x + 1];  // first query row (within seq) of this tile
   const int head = blockIdx.y;
   const int kvh = head / (nh / nkv);
+  [[maybe_unused]] float v_scale = 1.f;
+  if constexpr (FP8) {
+    const float* sc = pack_ptr(kv_scale...);
+    scale_log2 *= sc[kvh];
+    v_scale = sc[nkv + kvh];
+  }
+  [[maybe_unused]] const uint8_t* k8 = reinterpret_cast<const uint8_t*>(k_cache);
+  [[maybe_unused]] const uint8_t* v8 = reinterpret_cast<const uint8_t*>(v_cache);
   const int q0 = cu_seqlens_q[b];
   const int qlen = cu_seqlens_q[b + 1] - q0;
   const int ctx = context_lens[b];
@@ -125,7 +141,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
   // the global loads of tile i+1 are in flight while tile i is consumed from
   // LDS (1 workgroup per CU at this register budget, so latency must be hidden
   // inside the wave, not by occupancy).
-  u32x4 kr[NP], vr[NP];
+  using raw_t = typename std::conditional<FP8, uint2, u32x4>::type;   // fp8: 8 codes per chunk
+  raw_t kr[NP], vr[NP];
   auto load_tile = [&](int kb0) {
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -134,8 +151,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
       const int key = min(kb0 + row, kv_end - 1);
       const int blk = bt[key >> bs_log2];
       const size_t base = ((size_t)blk * nkv + kvh) * head_stride + (size_t)(key & (bs - 1)) * HD + ch * 8;
-      kr[p] = *reinterpret_cast<const u32x4*>(k_cache + base);
-      vr[p] = *reinterpret_cast<const u32x4*>(v_cache + base);
+      if constexpr (FP8) {
+        kr[p] = *reinterpret_cast<const uint2*>(k8 + base);
+        vr[p] = *reinterpret_cast<const uint2*>(v8 + base);
+      } else {
+        kr[p] = *reinterpret_cast<const u32x4*>(k_cache + base);
+        vr[p] = *reinterpret_cast<const u32x4*>(v_cache + base);
+      }
     }
   };
   auto store_tile = [&](uint16_t* kst, uint16_t* vst) {
@@ -143,8 +165,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
     for (int p = 0; p < NP; ++p) {
       const int row = p * (NT / CH) + tid / CH;
       const int ch = tid % CH;
-      *reinterpret_cast<u32x4*>(kst + k_off<HD>(row, ch)) = kr[p];
-      *reinterpret_cast<u32x4*>(vst + v_off<HD>(row, ch)) = vr[p];
+      if constexpr (FP8) {
+        *reinterpret_cast<u32x4*>(kst + k_off<HD>(row, ch)) = widen8_u32(kr[p].x, kr[p].y);
+        *reinterpret_cast<u32x4*>(vst + v_off<HD>(row, ch)) = widen8_u32(vr[p].x, vr[p].y);
+      } else {
+        *reinterpret_cast<u32x4*>(kst + k_off<HD>(row, ch)) = kr[p];
+        *reinterpret_cast<u32x4*>(vst + v_off<HD>(row, ch)) = vr[p];
+      }
     }
   };
   // Full tiles of 16-token pages (the engine's page size): the rows one wave stages in one
@@ -172,8 +199,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const size_t base = ((size_t)nbt[p] * nkv + kvh) * head_stride;
-      kr[p] = *reinterpret_cast<const u32x4*>(k_cache + base + lane_off);
-      vr[p] = *reinterpret_cast<const u32x4*>(v_cache + base + lane_off);
+      if constexpr (FP8) {
+        kr[p] = *reinterpret_cast<const uint2*>(k8 + base + lane_off);
+        vr[p] = *reinterpret_cast<const uint2*>(v8 + base + lane_off);
+      } else {
+        kr[p] = *reinterpret_cast<const u32x4*>(k_cache + base + lane_off);
+        vr[p] = *reinterpret_cast<const u32x4*>(v_cache + base + lane_off);
+      }
     }
   };
   auto load_any = [&](int kb0) {
@@ -345,7 +377,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
   }
 
   if (!row_valid) return;
-  const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+  float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+  if constexpr (FP8) inv *= v_scale;
   uint16_t* op = out + (size_t)(q0 + my_row) * out_stride + head * HD;
 #pragma unroll
   for (int d = 0; d < ND; ++d)
@@ -368,7 +401,7 @@ extern "C" int dgi_paged_prefill(const void* q, int q_stride, const void* k_cach
                                  const int* cu_seqlens_q, const int* context_lens, const int* tiles,
                                  int n_tiles, void* out, int out_stride, int nh, int nkv, int hd,
                                  int block_size, float scale, const unsigned long long* tree_mask,
-                                 int tree_n, int tile_rows, hipStream_t s) {
+                                 int tree_n, int tile_rows, const float* kv_scale, hipStream_t s) {
   if (n_tiles == 0) return 0;
   if (hd != 128 && hd != 64) return -5;
   if (nh % nkv) return -2;
@@ -380,11 +413,20 @@ extern "C" int dgi_paged_prefill(const void* q, int q_stride, const void* k_cach
   const int db = (tile_rows >> 16) & 1;          // bit 16: two LDS stages (prefill_attn_kernel DB)
   tile_rows &= 0xffff;
   if (tile_rows != 128 && tile_rows != 256) return -7;
+  // kv_scale != nullptr: the caches hold e4m3 codes
 #define DGI_PREFILL(HDV, NWV, DBV)                                                                     \
-  prefill_attn_kernel<HDV, NWV, DBV><<<dim3(n_tiles, nh), NWV * 64, 0, s>>>(                           \
-      (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,     \
-      bt_stride, cu_seqlens_q, context_lens, tiles, (uint16_t*)out, out_stride, nh, nkv, bs_log2,         \
-      scale_log2, tree_mask, tree_n)
+  do {                                                                                                 \
+    if (kv_scale)                                                                                      \
+      prefill_attn_kernel<HDV, NWV, DBV, true, const float*><<<dim3(n_tiles, nh), NWV * 64, 0, s>>>(   \
+          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,            \
+          block_tables, bt_stride, cu_seqlens_q, context_lens, tiles, (uint16_t*)out, out_stride, nh,  \
+          nkv, bs_log2, scale_log2, tree_mask, tree_n, kv_scale);                                      \
+    else                                                                                               \
+      prefill_attn_kernel<HDV, NWV, DBV, false><<<dim3(n_tiles, nh), NWV * 64, 0, s>>>(                \
+          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,            \
+          block_tables, bt_stride, cu_seqlens_q, context_lens, tiles, (uint16_t*)out, out_stride, nh,  \
+          nkv, bs_log2, scale_log2, tree_mask, tree_n);                                                \
+  } while (0)
   if (hd == 128) {
     if (tile_rows == 256) { if (db) DGI_PREFILL(128, 8, 1); else DGI_PREFILL(128, 8, 0); }
     else { if (db) DGI_PREFILL(128, 4, 1); else DGI_PREFILL(128, 4, 0); }

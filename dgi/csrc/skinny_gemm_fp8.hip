@@ -31,24 +31,6 @@ struct Frag8 {
   u32x4 x[U][MT][4];
 };
 
-// 8 e4m3 (two words) -> 8 bf16 (one MFMA operand)
-__device__ __forceinline__ uint32_t widen2(uint32_t word, bool hi) {
-  const f32x2v f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)word, true)
-                      : __builtin_amdgcn_cvt_pk_f32_fp8((int)word, false);
-  // upper halves of the two words, f[0] low (v_perm_b32: selector bytes 0-3 index the second
-  // source, 4-7 the first); exact: an e4m3 value has 3 mantissa bits, bf16 keeps 7
-  return __builtin_amdgcn_perm(__float_as_uint(f[1]), __float_as_uint(f[0]), 0x07060302u);
-}
-
-__device__ __forceinline__ bf16x8 widen8(uint32_t a, uint32_t b) {
-  u32x4 r;
-  r[0] = widen2(a, false);
-  r[1] = widen2(a, true);
-  r[2] = widen2(b, false);
-  r[3] = widen2(b, true);
-  return as_bf16x8(r);
-}
-
 template <int NW, int MT, int NT, int U, int D>
 __global__ __launch_bounds__(NW * 64) void skinny_gemm_w8_kernel(
     const uint16_t* __restrict__ X, int ldx, const uint8_t* __restrict__ W, const float* __restrict__ scale,

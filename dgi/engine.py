@@ -8,6 +8,7 @@ the reference's ``LLMBaseEngine`` contract (worker/engines/llm_base.py:45-188).
 from __future__ import annotations
 
 import dataclasses
+import logging
 import math
 import time
 from typing import Iterable, Optional
@@ -25,6 +26,23 @@ from dgi.utils.trace import phase
 
 
 WEIGHT_QUANT_MODES = (None, "fp8")
+KV_DTYPES = (None, "fp8")      # None: KV pages in the activation dtype; "fp8": e4m3 codes + per-head scales
+logger = logging.getLogger(__name__)
+
+
+def refuse_fp8_kv(cfg, what: str) -> None:
+    """Layouts that move or share KV in ways the fp8 pool does not cover yet refuse it at
+    configuration time (``what`` names the layout)."""
+    if getattr(cfg, "kv_dtype", None) == "fp8":
+        raise ValueError(f"kv_dtype='fp8' is not supported with {what}: serve it from a single-GPU "
+                         "LLMEngine, or leave kv_dtype unset for a bf16 KV cache")
+
+
+def _refuse_fp8_kv_layout(model) -> None:
+    if getattr(model, "reduce", None) is not None or getattr(model, "tp", 1) > 1:
+        raise ValueError("kv_dtype='fp8' is not supported with tensor parallel")
+    if getattr(model, "layer_start", 0) != 0 or getattr(model, "layer_end", model.cfg.num_layers) != model.cfg.num_layers:
+        raise ValueError("kv_dtype='fp8' is not supported with a layer pipeline (partial layer range)")
 
 
 @dataclasses.dataclass
@@ -55,8 +73,12 @@ class EngineConfig:
     decode_lookahead: bool = True      # pure-decode graph steps: launch step N+1 before step N's
                                        # tokens are back (``LLMEngine._lookahead``); DGI_DECODE_LOOKAHEAD=0
     weight_quant: Optional[str] = None   # "fp8": weight-only e4m3 projections (``LlamaModel.quantize_weights``)
+    kv_dtype: Optional[str] = None       # "fp8": e4m3 KV pages with per-head scales (``BlockPool.kv_scale``)
 
     def __post_init__(self):
+        if self.kv_dtype not in KV_DTYPES:
+            raise ValueError(f"EngineConfig.kv_dtype={self.kv_dtype!r}: supported values are "
+                             f"{', '.join(repr(m) for m in KV_DTYPES)}")
         if self.weight_quant not in WEIGHT_QUANT_MODES:
             raise ValueError(f"EngineConfig.weight_quant={self.weight_quant!r}: supported values are "
                              f"{', '.join(repr(m) for m in WEIGHT_QUANT_MODES)}")
@@ -78,6 +100,11 @@ def _device_free_bytes(device: torch.device) -> int:
     return 2 << 30
 
 
+def kv_pool_dtype(cfg: EngineConfig) -> torch.dtype:
+    """Element type of the engine's KV pages: the activation dtype, or e4m3 codes for ``kv_dtype="fp8"``."""
+    return torch.float8_e4m3fn if cfg.kv_dtype == "fp8" else cfg.dtype
+
+
 def engine_block_budget(cfg: EngineConfig, mc: ModelConfig, n_local: int, device: torch.device) -> int:
     """KV pages for this engine: ``kv_fraction`` of free HBM after weights and the
     activation workspace, capped by what ``max_num_seqs`` full sequences can use."""
@@ -87,7 +114,8 @@ def engine_block_budget(cfg: EngineConfig, mc: ModelConfig, n_local: int, device
         budget = max(0, _device_free_bytes(device) - cfg.workspace_bytes) * cfg.kv_fraction
     else:
         budget = 1 << 30  # CPU rehearsal runs: a fixed 1 GiB pool
-    nblocks = num_blocks_for_budget(int(budget), max(1, n_local), mc.num_kv_heads, mc.head_dim, cfg.block_size)
+    nblocks = num_blocks_for_budget(int(budget), max(1, n_local), mc.num_kv_heads, mc.head_dim, cfg.block_size,
+                                    dtype_bytes=torch.tensor([], dtype=kv_pool_dtype(cfg)).element_size())
     # never more than what max_num_seqs full-length sequences can use (+ prefix cache room)
     cap = 2 * cfg.max_num_seqs * ((cfg.max_model_len + cfg.block_size - 1) // cfg.block_size) + 1
     return max(2, min(nblocks, cap))
@@ -135,8 +163,17 @@ class LLMEngine:
         mc = self.model_cfg
         n_local = self.model.num_local_layers
         nblocks = engine_block_budget(cfg, mc, n_local, self.device)
+        if cfg.kv_dtype == "fp8":
+            _refuse_fp8_kv_layout(self.model)
         self.pool = BlockPool(nblocks, cfg.block_size, max(1, n_local), mc.num_kv_heads, mc.head_dim,
-                              cfg.dtype, self.device)
+                              kv_pool_dtype(cfg), self.device)
+        if self.pool.is_fp8:
+            # per-layer k_scale / v_scale of the checkpoint (vLLM / compressed-tensors convention), else ones
+            ckpt_scales = getattr(self.model, "kv_scales_loaded", None)
+            if ckpt_scales is not None:
+                self.pool.set_kv_scales(ckpt_scales)
+            else:
+                logger.info("fp8 KV cache: no self_attn.k_scale / v_scale in the checkpoint, the scales are ones")
         align = cfg.token_align if cfg.token_align >= 0 else (256 if self.device.type == "cuda" else 0)
         self.scheduler = Scheduler(self.pool, SchedulerConfig(cfg.max_num_seqs, cfg.max_num_batched_tokens,
                                                               cfg.max_model_len, cfg.enable_prefix_caching,
@@ -264,7 +301,7 @@ class LLMEngine:
             outs = self._step_mixed_lookahead()
             self._account(n, time.perf_counter() - t0)
             return outs
-        self.model.kv_cache = self.pool.kv   # engines may share one model object
+        self.model.bind_kv(self.pool)   # engines may share one model object
         with phase("schedule"):
             sbud = self.step_budget
             cap = None
@@ -536,17 +573,30 @@ class LLMEngine:
         return ops.kv_gather(self.pool.kv, ids).cpu()
 
     def import_prefilled(self, prompt: list[int], first_token: int, kv: torch.Tensor,
-                         params: Optional[SamplingParams] = None, rid=None, seed: Optional[int] = None) -> Request:
+                         params: Optional[SamplingParams] = None, rid=None, seed: Optional[int] = None,
+                         kv_scale: Optional[torch.Tensor] = None) -> Request:
         """Adopt a sequence another worker prefilled: its pages ``kv`` (``export_request_kv``
         layout) go into fresh pages of this pool and decoding continues from
         ``first_token`` — no prompt recompute.  ``seed``: the exporting request's
         sampling seed (a seeded request then draws the same tokens as on one
         worker).  The first token goes through the same stop checks as a local
         one: a sequence that ended there (EOS / stop id / max_tokens) comes back
-        FINISHED with its pages released."""
+        FINISHED with its pages released.  Pages of an fp8 pool are codes: they are taken only
+        by an fp8 pool whose scales equal ``kv_scale`` (the exporter's), never converted."""
         from dgi import ops
         L, two, n, nkv, bs, hd = kv.shape
         pool = self.pool
+        fp8 = torch.float8_e4m3fn
+        if (kv.dtype == fp8) != (pool.dtype == fp8):
+            raise ValueError(f"KV pages of dtype {kv.dtype} offered to a pool of {pool.dtype}: an fp8 KV cache "
+                             "is exchanged only between engines with kv_dtype='fp8'")
+        if pool.dtype == fp8:
+            if kv_scale is None:
+                raise ValueError("fp8 KV pages without their scales (the exporter's BlockPool.kv_scale)")
+            mine = pool.kv_scale.cpu()
+            theirs = torch.as_tensor(kv_scale, dtype=torch.float32).cpu()
+            if tuple(theirs.shape) != tuple(mine.shape) or not torch.equal(theirs, mine):
+                raise ValueError("fp8 KV pages were written with scales that differ from this pool's kv_scale")
         if (L, nkv, bs, hd) != (pool.kv.shape[0], pool.kv.shape[3], pool.kv.shape[4], pool.kv.shape[5]):
             raise ValueError(f"KV geometry {tuple(kv.shape)} does not match this engine's pool "
                              f"{tuple(pool.kv.shape)}")

@@ -1,7 +1,7 @@
 """Paged KV block pool (SURVEY §2.2 ``PagedKVCache``/``KVCachePool`` equivalent).
 
 Physical storage is ONE device tensor ``[L_local, 2, num_blocks, n_kv, bs, hd]``
-(bf16) so a block id names the page of every local layer: a sequence needs
+(bf16, or e4m3 codes with per-head scales: see ``kv_scale``) so a block id names the page of every local layer: a sequence needs
 ``ceil(len/bs)`` ids, not ``L*ceil(len/bs)`` as in the reference's per-layer
 pools (worker/distributed/kv_cache.py:250-323).  Allocation is an O(1)
 free-list pop with reference counts for prefix sharing (radix cache,
@@ -43,12 +43,45 @@ class BlockPool:
         if allocate:
             self.kv = torch.zeros(num_layers, 2, num_blocks, num_kv_heads, block_size, head_dim,
                                   dtype=dtype, device=self.device)
+        # fp8 pages (``torch.float8_e4m3fn``): value = float(code) * kv_scale[layer, K/V, kv head];
+        # the writer multiplies by kv_inv_scale, computed once here as 1 / kv_scale in fp32, so the
+        # HIP writer and the reference use the same stored inverse
+        self.kv_scale: Optional[torch.Tensor] = None
+        self.kv_inv_scale: Optional[torch.Tensor] = None
+        if self.is_fp8:
+            self.set_kv_scales(torch.ones(num_layers, 2, num_kv_heads, dtype=torch.float32))
+        elif dtype.is_floating_point and torch.tensor([], dtype=dtype).element_size() < 2:
+            raise ValueError(f"BlockPool: unsupported KV dtype {dtype} (bfloat16/float16/float32 or float8_e4m3fn)")
         # block 0 is reserved as a scratch/padding page (graph padding rows write there)
         self._free: list[int] = list(range(num_blocks - 1, 0, -1))
         self.ref = [0] * num_blocks
         self.ref[0] = 1 << 30
         self.evictor = None  # callable(n) -> frees >= n blocks (radix cache LRU)
         self.stats = {"allocs": 0, "frees": 0, "evictions": 0, "cow": 0}
+
+    @property
+    def is_fp8(self) -> bool:
+        return self.dtype == torch.float8_e4m3fn
+
+    def set_kv_scales(self, scale: torch.Tensor) -> None:
+        """Install ``[L, 2, n_kv]`` scales (positive, finite) and recompute the stored inverses.
+        Pages already written keep the codes of the old scales: set them before any request."""
+        if not self.is_fp8:
+            raise ValueError(f"set_kv_scales: the pool's dtype is {self.dtype}, not float8_e4m3fn")
+        want = (self.num_layers, 2, self.num_kv_heads)
+        scale = torch.as_tensor(scale, dtype=torch.float32)
+        if tuple(scale.shape) != want:
+            raise ValueError(f"set_kv_scales: expected shape {want}, got {tuple(scale.shape)}")
+        if not bool((torch.isfinite(scale) & (scale > 0)).all()):
+            raise ValueError("set_kv_scales: scales must be positive and finite")
+        scale = scale.detach().to("cpu").contiguous().clone()
+        inv = (torch.ones((), dtype=torch.float32) / scale).contiguous()
+        if self.kv_scale is None:
+            self.kv_scale = scale.to(self.device)
+            self.kv_inv_scale = inv.to(self.device)
+        else:       # in place: the model and captured graphs hold views of these tensors
+            self.kv_scale.copy_(scale)
+            self.kv_inv_scale.copy_(inv)
 
     # ------------------------------------------------------------------ state
     @property

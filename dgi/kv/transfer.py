@@ -15,7 +15,9 @@ Wire format: ``b"DGKV"`` | u32 header length | JSON header | raw page bytes.
 The header carries the tensor shape and dtype, the prompt token ids, the first
 token and the model geometry the importer checks; bf16 travels as its raw 16-bit
 pattern (lossless, unlike the reference serializer's fp16 round trip,
-common/serialization.py).
+common/serialization.py).  Pages of an fp8 pool travel as their e4m3 codes, one byte
+each, with the pool's ``[L, 2, n_kv]`` scales in the header (``kv_scale``): the importer
+refuses pages whose dtype or scales differ from its own pool's.
 """
 from __future__ import annotations
 
@@ -31,22 +33,31 @@ import torch
 
 MAGIC = b"DGKV"
 _DT = {torch.bfloat16: ("bfloat16", torch.int16), torch.float16: ("float16", torch.int16),
-       torch.float32: ("float32", torch.float32)}
+       torch.float32: ("float32", torch.float32), torch.float8_e4m3fn: ("float8_e4m3fn", torch.uint8)}
 _DT_BACK = {"bfloat16": (torch.bfloat16, np.int16), "float16": (torch.float16, np.int16),
-            "float32": (torch.float32, np.float32)}
+            "float32": (torch.float32, np.float32), "float8_e4m3fn": (torch.float8_e4m3fn, np.uint8)}
 
 
-def pack_kv(kv: torch.Tensor, meta: dict) -> bytes:
-    """[L, 2, n_pages, n_kv, page, head_dim] pages + metadata -> one blob."""
+def pack_kv(kv: torch.Tensor, meta: dict, kv_scale: Optional[torch.Tensor] = None) -> bytes:
+    """[L, 2, n_pages, n_kv, page, head_dim] pages + metadata -> one blob.  fp8 pages need the
+    exporting pool's ``kv_scale`` [L, 2, n_kv]; it goes into the header (fp32 values survive
+    JSON exactly: they are written as the doubles they equal)."""
     kv = kv.detach().contiguous().cpu()
     name, view = _DT[kv.dtype]
     hdr = dict(meta, shape=list(kv.shape), dtype=name)
+    if kv.dtype == torch.float8_e4m3fn:
+        if kv_scale is None:
+            raise ValueError("pack_kv: fp8 pages need the pool's kv_scale")
+        hdr["kv_scale"] = kv_scale.detach().float().cpu().double().tolist()
+    elif kv_scale is not None:
+        raise ValueError(f"pack_kv: kv_scale given for {kv.dtype} pages")
     h = json.dumps(hdr).encode()
     return MAGIC + struct.pack("<I", len(h)) + h + kv.view(view).numpy().tobytes()
 
 
 def unpack_kv(blob: bytes) -> tuple:
-    """blob -> (pages tensor on the host, metadata dict)."""
+    """blob -> (pages tensor on the host, metadata dict).  The metadata of fp8 pages carries
+    ``kv_scale`` as an fp32 tensor [L, 2, n_kv] (hand it to ``LLMEngine.import_prefilled``)."""
     if blob[:4] != MAGIC:
         raise ValueError("not a dgi KV blob")
     (n,) = struct.unpack("<I", blob[4:8])
@@ -55,6 +66,8 @@ def unpack_kv(blob: bytes) -> tuple:
     shape = hdr.pop("shape")
     arr = np.frombuffer(blob, dtype=npdt, offset=8 + n, count=int(np.prod(shape)))
     t = torch.from_numpy(arr.copy()).view(dt).view(*shape)
+    if "kv_scale" in hdr:
+        hdr["kv_scale"] = torch.tensor(hdr["kv_scale"], dtype=torch.float64).float()
     return t, hdr
 
 

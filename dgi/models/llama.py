@@ -116,6 +116,10 @@ class LlamaModel:
         self.num_local_layers = self.layer_end - self.layer_start
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
         self.kv_cache: Optional[torch.Tensor] = None  # [L_local, 2, NB, nkv, bs, hd]
+        # fp8 KV pool (float8_e4m3fn pages): its per (layer, K/V, kv head) scales and their stored
+        # inverses, [L_local, 2, nkv] fp32 each (``bind_kv``); unused with a bf16 pool
+        self.kv_scale: Optional[torch.Tensor] = None
+        self.kv_inv_scale: Optional[torch.Tensor] = None
         self.layers: list[LlamaLayerWeights] = []
         self.embed = self.norm = self.lm_head = None
         # EAGLE-3 feature taps: global layer ids whose output residual stream is kept
@@ -339,15 +343,32 @@ class LlamaModel:
             n += self.lm_head.numel() * self.lm_head.element_size()
         return n
 
+    def bind_kv(self, pool) -> None:
+        """Point the model at a ``BlockPool``'s pages (and, for an fp8 pool, its scales)."""
+        self.kv_cache = pool.kv
+        self.kv_scale = getattr(pool, "kv_scale", None)
+        self.kv_inv_scale = getattr(pool, "kv_inv_scale", None)
+
+    @property
+    def kv_fp8(self) -> bool:
+        return self.kv_cache is not None and ops.is_fp8_kv(self.kv_cache)
+
     # ------------------------------------------------------------------ forward
     def attention(self, li: int, qkv: torch.Tensor, meta: AttnMeta, rope: bool = True,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
         c = self.cfg
         kc = self.kv_cache[li, 0]
         vc = self.kv_cache[li, 1]
+        ksc = kinv = None
+        if self.kv_fp8:
+            if not rope:
+                raise RuntimeError("fp8 KV cache: the RoPE + KV-write GEMM epilogues have no fp8 writer")
+            if self.kv_scale is None or self.kv_scale.shape[0] != self.kv_cache.shape[0]:
+                raise RuntimeError("fp8 KV cache without its scales: bind the pool with LlamaModel.bind_kv")
+            ksc, kinv = self.kv_scale[li], self.kv_inv_scale[li]
         if rope:       # else the qkv GEMM epilogue already rotated q/k and wrote the cache
             ops.rope_cache(qkv, meta.positions, self.cos_sin, c.num_heads, c.num_kv_heads, c.head_dim,
-                           meta.slot_mapping, kc, vc, self.rope_mode)
+                           meta.slot_mapping, kc, vc, self.rope_mode, kv_inv_scale=kinv)
         T = qkv.shape[0]
         if out is None:
             out = torch.empty(T, c.q_size, device=qkv.device, dtype=qkv.dtype)
@@ -367,11 +388,11 @@ class LlamaModel:
             with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
                 ops.paged_decode(qkv[:nd], kc, vc, meta.dec_block_tables, meta.dec_context_lens, c.num_heads,
                                  c.num_kv_heads, self.scale, meta.dec_max_splits, meta.dec_part_size,
-                                 out=out[:nd], workspace=meta.dec_workspace)
+                                 out=out[:nd], workspace=meta.dec_workspace, kv_scale=ksc)
         if meta.num_prefill_tokens > 0:
             ops.paged_prefill(qkv[nd:], kc, vc, meta.pre_block_tables, meta.pre_cu_seqlens, meta.pre_context_lens,
                               c.num_heads, c.num_kv_heads, self.scale, tiles=meta.pre_tiles,
-                              tree_mask=meta.tree_mask, tree_n=meta.tree_n, out=out[nd:])
+                              tree_mask=meta.tree_mask, tree_n=meta.tree_n, out=out[nd:], kv_scale=ksc)
         if side is not None:
             main.wait_stream(side)
         return out
@@ -451,7 +472,8 @@ class LlamaModel:
         c = self.cfg
         eps = c.rms_eps
         T = h.shape[0]
-        rope_epi = self.rope_mode == 0 and c.head_dim == 128 and self.cos_sin.shape[1] == 128
+        # the RoPE + KV-write epilogue writes bf16 pages only: an fp8 pool takes the plain epilogue + rope_cache
+        rope_epi = self.rope_mode == 0 and c.head_dim == 128 and self.cos_sin.shape[1] == 128 and not self.kv_fp8
         for i, L in enumerate(self.layers):
             kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
             if fuse_qkv:
@@ -543,7 +565,7 @@ class LlamaModel:
         n = len(self.layers)
         rope_epi = (NORM_FOLD_ROPE and (R.is_cuda or NORM_FOLD == "force-cpu") and self.rope_mode == 0 and c.head_dim == 128
                     and self.cos_sin.shape[1] == 128 and (c.num_heads * 128) % 256 == 0
-                    and (c.num_kv_heads * 128) % 256 == 0)
+                    and (c.num_kv_heads * 128) % 256 == 0 and not self.kv_fp8)
         for i, L in enumerate(self.layers):
             if rope_epi:
                 qkv = ops.mfma_gemm_norm_rope(R, L.qkv, ss, eps, meta.positions, self.cos_sin, meta.slot_mapping,

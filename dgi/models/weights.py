@@ -113,6 +113,24 @@ def _put(dst: torch.Tensor, src: torch.Tensor) -> None:
     dst.copy_(src.to(dst.dtype), non_blocking=False)
 
 
+def load_kv_scales(rd, layer_start: int, layer_end: int, num_kv_heads: int) -> Optional[torch.Tensor]:
+    """``[L_local, 2, n_kv]`` fp32 KV-cache scales from a checkpoint's per-layer
+    ``self_attn.k_scale`` / ``self_attn.v_scale`` scalars (the vLLM / compressed-tensors
+    convention), each broadcast over the kv heads; None when the checkpoint has none.  A layer
+    that lacks one of the two keeps 1.0 for it."""
+    names = [(f"model.layers.{li}.self_attn.k_scale", f"model.layers.{li}.self_attn.v_scale")
+             for li in range(layer_start, layer_end)]
+    if not any(k in rd or v in rd for k, v in names):
+        return None
+    out = torch.ones(len(names), 2, num_kv_heads, dtype=torch.float32)
+    for i, pair in enumerate(names):
+        for j, name in enumerate(pair):
+            if name in rd:
+                # scalars (0-d, or one element): whole-tensor read, not a slice
+                out[i, j] = float(rd._h(name).get_tensor(name).float().reshape(-1)[0])
+    return out
+
+
 def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
     """Fill a ``LlamaModel`` (created with ``init="empty"``) from an HF checkpoint.
 
@@ -167,6 +185,8 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
             else:   # tied checkpoint served by an untied slot (last stage without the embedding)
                 _put(model.lm_head, rd.read("model.embed_tokens.weight"))
             n += 1
+    # per-layer KV-cache scales, used only by an fp8 KV pool (``EngineConfig.kv_dtype``)
+    model.kv_scales_loaded = load_kv_scales(rd, model.layer_start, model.layer_end, c.num_kv_heads)
     out = {"tensors": n, "bytes": rd.bytes_read, "path": path}
     rd.close()
     return out

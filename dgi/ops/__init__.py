@@ -160,7 +160,55 @@ def _rope(x: torch.Tensor, cs: torch.Tensor, mode: int) -> torch.Tensor:
     return rot if rd == x.shape[-1] else torch.cat([rot, x[..., rd:]], dim=-1)
 
 
-def rope_cache_ref(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode: int = 0) -> None:
+# ---- fp8 KV cache: pages of OCP e4m3 codes (torch.float8_e4m3fn) with one fp32 scale per
+# (K or V, kv head).  ONE definition of the format, used by the references below, by the CPU
+# engine and as the oracle of the HIP writer:
+#   write: code  = rne_e4m3(clamp(float(x_bf16) * inv_scale, -448, 448)),  inv_scale = 1 / scale (fp32)
+#   read:  value = float(code) * scale
+KV_FP8 = torch.float8_e4m3fn
+KV_FP8_MAX = 448.0
+
+
+def is_fp8_kv(cache: torch.Tensor) -> bool:
+    return cache.dtype == KV_FP8
+
+
+def quantize_kv_ref(x: torch.Tensor, inv_scale: torch.Tensor) -> torch.Tensor:
+    """e4m3 codes of ``x`` [..., n_kv, hd] (or any shape ``inv_scale[:, None]`` broadcasts against).
+
+    ``inv_scale`` is the stored fp32 inverse ``[n_kv]`` (a 0-d tensor or a float also works).
+    The clamp is explicit: torch's own cast turns anything past 448 into NaN."""
+    inv = torch.as_tensor(inv_scale, dtype=torch.float32, device=x.device)
+    if inv.dim() == 1:
+        inv = inv[:, None]
+    return torch.clamp(x.float() * inv, -KV_FP8_MAX, KV_FP8_MAX).to(KV_FP8)
+
+
+def dequantize_kv_ref(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 values of e4m3 ``codes`` [..., n_kv, hd]; ``scale`` is ``[n_kv]`` fp32."""
+    sc = torch.as_tensor(scale, dtype=torch.float32, device=codes.device)
+    if sc.dim() == 1:
+        sc = sc[:, None]
+    return codes.float() * sc
+
+
+def _kv_scale_for(cache: torch.Tensor, scale, what: str):
+    """The [2, n_kv] fp32 scale tensor an fp8 cache is used with (ones when none is given);
+    None for a bf16 cache, which takes no scales."""
+    if not is_fp8_kv(cache):
+        if scale is not None:
+            raise ValueError(f"{what}: scales given for a {cache.dtype} KV cache")
+        return None
+    nkv = cache.shape[1]
+    if scale is None:
+        return torch.ones(2, nkv, dtype=torch.float32, device=cache.device)
+    if scale.dtype != torch.float32 or tuple(scale.shape) != (2, nkv):
+        raise ValueError(f"{what}: kv scales must be fp32 [2, {nkv}], got {scale.dtype} {tuple(scale.shape)}")
+    return scale.contiguous()
+
+
+def rope_cache_ref(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode: int = 0,
+                   kv_inv_scale=None) -> None:
     T = qkv.shape[0]
     if T == 0:
         return
@@ -177,42 +225,56 @@ def rope_cache_ref(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, 
     if ok.any():
         s = slots[ok]
         blk, off = s // bs, s % bs
-        k_cache[blk, :, off] = kr[ok]
-        v_cache[blk, :, off] = v[ok]
+        inv = _kv_scale_for(k_cache, kv_inv_scale, "rope_cache")
+        if inv is None:
+            k_cache[blk, :, off] = kr[ok]
+            v_cache[blk, :, off] = v[ok]
+        else:
+            # the values the bf16 cache would hold (k rounded to the activation dtype), then the quantiser
+            k_cache[blk, :, off] = quantize_kv_ref(kr[ok], inv[0])
+            v_cache[blk, :, off] = quantize_kv_ref(v[ok], inv[1])
 
 
-def rope_cache(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode: int = 0) -> None:
+def rope_cache(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode: int = 0,
+               kv_inv_scale=None) -> None:
     """Rotate q in place inside the fused qkv rows, write rotated k and v into the paged cache.
 
     ``cos_sin`` is [max_pos, rd] (rd <= hd rotary dims); ``mode`` 0 = NeoX
-    pairing (Llama, Qwen2), 1 = interleaved pairs (GLM-4, GPT-J)."""
+    pairing (Llama, Qwen2), 1 = interleaved pairs (GLM-4, GPT-J).  An fp8 cache
+    (``float8_e4m3fn``) is written as e4m3 codes; ``kv_inv_scale`` is the layer's
+    stored inverse scales ``[2, n_kv]`` fp32 (``BlockPool.kv_inv_scale[layer]``; ones if None)."""
     if _native(qkv):
-        _call("rope_cache", qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode)
+        inv = _kv_scale_for(k_cache, kv_inv_scale, "rope_cache")
+        _call("rope_cache", qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode, inv)
     else:
-        rope_cache_ref(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode)
+        rope_cache_ref(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode, kv_inv_scale)
 
 
 # ----------------------------------------------------------------------------
 # Attention
 # ----------------------------------------------------------------------------
 
-def _gather_kv(k_cache, v_cache, bt_row, ctx):
+def _gather_kv(k_cache, v_cache, bt_row, ctx, kv_scale=None):
+    """[ctx, n_kv, hd] K and V of one sequence; an fp8 cache comes back dequantised (fp32)."""
     bs = k_cache.shape[2]
     nblk = (ctx + bs - 1) // bs
     ids = bt_row[:nblk].long()
     k = k_cache[ids].permute(0, 2, 1, 3).reshape(nblk * bs, k_cache.shape[1], -1)[:ctx]
     v = v_cache[ids].permute(0, 2, 1, 3).reshape(nblk * bs, v_cache.shape[1], -1)[:ctx]
+    sc = _kv_scale_for(k_cache, kv_scale, "paged attention")
+    if sc is not None:
+        k, v = dequantize_kv_ref(k, sc[0]), dequantize_kv_ref(v, sc[1])
     return k, v
 
 
-def paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale) -> torch.Tensor:
+def paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale, kv_scale=None) -> torch.Tensor:
     hd = k_cache.shape[-1]
     B = q.shape[0]
     out = torch.empty(B, nh * hd, dtype=q.dtype, device=q.device)
     G = nh // nkv
     for b in range(B):
         ctx = int(context_lens[b])
-        k, v = _gather_kv(k_cache, v_cache, block_tables[b], ctx)
+        k, v = _gather_kv(k_cache, v_cache, block_tables[b], ctx, kv_scale)
         qb = q[b, : nh * hd].float().view(nkv, G, hd)
         s = torch.einsum("hgd,thd->hgt", qb, k.float()) * scale
         p = torch.softmax(s, dim=-1)
@@ -236,7 +298,8 @@ def decode_split_plan(batch: int, max_ctx: int, nkv: int, num_cus: int = 256) ->
 
 
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale,
-                 max_splits: int = 1, part_size: int = 1 << 30, out=None, workspace=None) -> torch.Tensor:
+                 max_splits: int = 1, part_size: int = 1 << 30, out=None, workspace=None,
+                 kv_scale=None) -> torch.Tensor:
     """Single-token attention for each row of ``q`` over its paged context.
 
     ``part_size > 0``: fixed parts; ``max_splits``/``part_size`` must cover the
@@ -245,7 +308,8 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale
     tokens (what captured graphs use).  With ``max_splits > 1`` a workspace
     ``(part_o[B*nh*splits*hd], part_lse[B*nh*splits][, counters[B*nkv] int32 zeros])``
     is used; with counters the last workgroup of each (sequence, kv-head)
-    combines the splits (no reduce kernel).
+    combines the splits (no reduce kernel).  An fp8 cache (``float8_e4m3fn``) is read as
+    e4m3 codes times ``kv_scale`` (the layer's ``[2, n_kv]`` fp32 scales; ones if None).
     """
     if _native(q):
         hd = k_cache.shape[-1]
@@ -265,9 +329,9 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale
             if part_size > 0:
                 part_size = max(128, ((part_size if part_size < (1 << 30) else 1 << 20) + 127) // 128 * 128)
         _call("paged_decode", out, q, k_cache, v_cache, block_tables, context_lens, po, pl,
-              nh, nkv, max_splits, part_size, scale, cnt)
+              nh, nkv, max_splits, part_size, scale, cnt, _kv_scale_for(k_cache, kv_scale, "paged_decode"))
         return out
-    r = paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale)
+    r = paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale, kv_scale)
     if out is not None:
         out.copy_(r)
         return out
@@ -275,7 +339,7 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale
 
 
 def paged_prefill_ref(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens, nh, nkv, scale,
-                      tree_mask=None, tree_n: int = 0) -> torch.Tensor:
+                      tree_mask=None, tree_n: int = 0, kv_scale=None) -> torch.Tensor:
     hd = k_cache.shape[-1]
     T = q.shape[0]
     out = torch.zeros(T, nh * hd, dtype=q.dtype, device=q.device)
@@ -287,7 +351,7 @@ def paged_prefill_ref(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_l
         if ql == 0:
             continue
         ctx = int(context_lens[b])
-        k, v = _gather_kv(k_cache, v_cache, block_tables[b], ctx)
+        k, v = _gather_kv(k_cache, v_cache, block_tables[b], ctx, kv_scale)
         qb = q[q0:q1, : nh * hd].float().view(ql, nkv, G, hd)
         s = torch.einsum("qhgd,thd->hgqt", qb, k.float()) * scale
         qpos = torch.arange(ctx - ql, ctx, device=q.device)
@@ -347,8 +411,9 @@ def prefill_tiles(cu_seqlens_q: list[int], tile: int = 0, context_lens=None) -> 
 
 
 def paged_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens, nh, nkv, scale,
-                  tiles=None, tree_mask=None, tree_n: int = 0, out=None) -> torch.Tensor:
-    """Causal varlen attention of packed queries over the paged KV (prefix + new)."""
+                  tiles=None, tree_mask=None, tree_n: int = 0, out=None, kv_scale=None) -> torch.Tensor:
+    """Causal varlen attention of packed queries over the paged KV (prefix + new).  An fp8 cache
+    is read as e4m3 codes times ``kv_scale`` (``[2, n_kv]`` fp32; ones if None)."""
     if _native(q) and k_cache.shape[-1] not in (64, 128):
         _warn_once("paged_prefill", f"head_dim {k_cache.shape[-1]}: the MFMA prefill kernel is built for 64 / 128; "
                                     "using the PyTorch reference")
@@ -361,10 +426,10 @@ def paged_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens,
             tiles = torch.tensor(tl if tl else [[0, 0]], dtype=torch.int32, device=q.device)[: len(tl)]
         _call("paged_prefill", out, q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens,
               tiles, nh, nkv, scale, tree_mask, tree_n,
-              PREFILL_TILE | ((PREFILL_DB & 1) << 16))
+              PREFILL_TILE | ((PREFILL_DB & 1) << 16), _kv_scale_for(k_cache, kv_scale, "paged_prefill"))
         return out
     r = paged_prefill_ref(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens, nh, nkv, scale,
-                          tree_mask, tree_n)
+                          tree_mask, tree_n, kv_scale)
     if out is not None:
         out.copy_(r)
         return out
@@ -590,7 +655,9 @@ def fused_skinny(y, x, res, res_out, gamma, eps, w, bias, pro: int, epi: int, po
 
     epi 0 stores [M, N]; epi 1 is SwiGLU over w = [gate; up] (y is [M, I]);
     epi 2 applies NeoX RoPE to the q/k heads of a fused qkv output and writes k/v
-    into the paged cache at ``slots`` (head_dim 128, full rotary)."""
+    into the paged cache at ``slots`` (head_dim 128, full rotary; bf16 pages only)."""
+    if epi == 2 and k_cache is not None and is_fp8_kv(k_cache):
+        raise ValueError("fused_skinny: the RoPE + KV-write epilogue has no fp8 writer; use epi 0 + rope_cache")
     if _native(x):
         if cfg is None:
             cfg = fused_cfg("gate_up" if epi == 1 else "qkv", x.shape[0])
@@ -777,7 +844,9 @@ def mfma_gemm_norm_rope(x, w, ss, eps, positions, cos_sin, slots, k_cache, v_cac
     (mfma_gemm.hip EPI 5): returns y whose q columns are rotated (its k / v columns are NOT
     written — they go to ``k_cache`` / ``v_cache`` at ``slots``, which attention reads), i.e.
     ``mfma_gemm_norm(x, w, NORM_PLAIN, ss)`` followed by ``rope_cache`` in one kernel.  Llama
-    geometry: head dim 128, full NeoX rotary, cos_sin [max_pos, 128]."""
+    geometry: head dim 128, full NeoX rotary, cos_sin [max_pos, 128]; bf16 pages only."""
+    if is_fp8_kv(k_cache):
+        raise ValueError("mfma_gemm_norm_rope: no fp8 KV writer; use mfma_gemm_norm + rope_cache")
     if _native(x):
         if out is None:
             out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
@@ -939,6 +1008,12 @@ def topk(logits: torch.Tensor, k: int):
 # KV block movement
 # ----------------------------------------------------------------------------
 
+def _as16(t: torch.Tensor) -> torch.Tensor:
+    """The page-movement kernels copy 16-byte chunks of 16-bit elements: an fp8 cache or buffer
+    goes through them as bf16-typed bit patterns of half the head dim (a view, no copy)."""
+    return t.view(torch.bfloat16) if t.dtype == KV_FP8 else t
+
+
 def kv_gather(cache: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor] = None,
               block_major: bool = False) -> torch.Tensor:
     """cache [L,2,NB,...] -> [L,2,n,...] pages of ``ids`` (``block_major``: [n,L,2,...], every
@@ -948,7 +1023,7 @@ def kv_gather(cache: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor
             shape = ((ids.numel(), cache.shape[0], cache.shape[1]) if block_major else
                      (cache.shape[0], cache.shape[1], ids.numel())) + tuple(cache.shape[3:])
             out = torch.empty(shape, dtype=cache.dtype, device=cache.device)
-        _call("kv_gather", out, cache, ids, bool(block_major))
+        _call("kv_gather", _as16(out), _as16(cache), ids, bool(block_major))
         return out
     r = cache[:, :, ids.long()]
     if block_major:
@@ -961,7 +1036,7 @@ def kv_gather(cache: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor
 
 def kv_scatter(cache: torch.Tensor, ids: torch.Tensor, buf: torch.Tensor, block_major: bool = False) -> None:
     if _native(cache):
-        _call("kv_scatter", cache, ids, buf, bool(block_major))
+        _call("kv_scatter", _as16(cache), ids, _as16(buf), bool(block_major))
     elif block_major:
         cache[:, :, ids.long()] = buf.reshape(ids.numel(), cache.shape[0], cache.shape[1],
                                               *cache.shape[3:]).permute(1, 2, 0, 3, 4, 5)
@@ -972,7 +1047,7 @@ def kv_scatter(cache: torch.Tensor, ids: torch.Tensor, buf: torch.Tensor, block_
 def kv_copy(cache: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> None:
     """Copy pages src[i] -> dst[i] for every layer (src/dst sets must be disjoint)."""
     if _native(cache):
-        _call("kv_copy", cache, src, dst)
+        _call("kv_copy", _as16(cache), src, dst)
     else:
         cache[:, :, dst.long()] = cache[:, :, src.long()]
 

@@ -44,7 +44,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from dgi.engine import EngineConfig, LLMEngine, StepOutput
+from dgi.engine import EngineConfig, LLMEngine, StepOutput, refuse_fp8_kv
 from dgi.models.config import ModelConfig, get_config
 from dgi.models.llama import LlamaModel
 from dgi.kv.block_pool import BlockPool, OutOfBlocks, num_blocks_for_budget
@@ -263,6 +263,7 @@ class PipelineEngine(LLMEngine):
                  model_cfg: Optional[ModelConfig] = None, split: Optional[list] = None,
                  kv_sources: Optional[list] = None):
         from dgi.parallel.fabric import CtrlChannel
+        refuse_fp8_kv(cfg, "the layer pipeline")
         self.f = fabric
         self.ranks = list(stage_ranks)
         assert self.ranks[0] == fabric.rank
@@ -515,6 +516,7 @@ class StageWorker:
                  split: Optional[list] = None, microbatches: Optional[int] = None,
                  kv_sources: Optional[list] = None):
         from dgi.parallel.fabric import CtrlChannel
+        refuse_fp8_kv(cfg, "the layer pipeline")
         self.f = fabric
         self.mb_cap = max(1, cfg.max_num_seqs // (microbatches or len(stage_ranks)))
         self.ranks = list(stage_ranks)

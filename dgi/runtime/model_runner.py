@@ -115,7 +115,10 @@ class ModelRunner:
         self.max_tokens = max_num_batched_tokens
         self.num_cus = num_cus
         self.step_id = 0
-        model.kv_cache = pool.kv
+        if hasattr(model, "bind_kv"):
+            model.bind_kv(pool)      # pages and, for an fp8 pool, its scales
+        else:
+            model.kv_cache = pool.kv
         self.is_cuda = self.device.type == "cuda"
         # decode split-KV plan used by graphs (fixed) and workspaces
         self.graph_part = decode_part_size

@@ -101,7 +101,7 @@ class Router:
         cfg = EngineConfig(model=args.model, device=dev, max_num_seqs=args.max_num_seqs,
                            max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                            use_graphs=dev.startswith("cuda") and not args.no_graphs, seed=args.seed,
-                       weight_quant=args.weight_quant)
+                       weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
         self.drv = None
         self.chans = {}
         self.load = collections.Counter()
@@ -337,7 +337,7 @@ def _prefill_loop(args, fabric, layout) -> None:
     cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=64 + cap,
                        max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                        use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed,
-                       weight_quant=args.weight_quant)
+                       weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
     srv = PrefillServer(cfg, fabric, layout, local_cap=cap, report_tokens=True)
     inbox = CtrlChannel(fabric, layout.drivers[0], 1, tag="req")
     stopping = False
@@ -368,7 +368,7 @@ def _replica_loop(args, fabric, layout) -> None:
     cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=args.max_num_seqs,
                        max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                        use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed,
-                       weight_quant=args.weight_quant)
+                       weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
     drv = DecodeDriver(cfg, fabric, layout)
     drv.track_arrivals = True
     drv.forward_tokens = True
@@ -402,6 +402,9 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weight-quant", default=None, choices=["fp8"],
                     help="weight-only quantisation of the layer projections (default: bf16 weights)")
+    ap.add_argument("--kv-dtype", default=None, choices=["fp8"],
+                    help="KV cache pages as e4m3 codes with per-head scales (default: bf16 pages); "
+                         "single-GPU engines only")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     fabric = layout = None
@@ -428,7 +431,7 @@ def main(argv=None) -> int:
             cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=args.max_num_seqs,
                                max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                                use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs,
-                               seed=args.seed, enable_prefix_caching=False, weight_quant=args.weight_quant)
+                               seed=args.seed, enable_prefix_caching=False, weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
             w = StageWorker(cfg, fabric, layout.group_of(fabric.rank), kv_sources=layout.prefill_ranks)
             while w.run() != "stop":
                 pass

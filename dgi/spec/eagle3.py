@@ -52,7 +52,7 @@ import torch
 import torch.nn.functional as F
 
 from dgi import ops
-from dgi.engine import EngineConfig, LLMEngine, StepOutput
+from dgi.engine import EngineConfig, LLMEngine, StepOutput, refuse_fp8_kv
 from dgi.kv.block_pool import OutOfBlocks
 from dgi.models.config import ModelConfig
 from dgi.models.llama import LlamaModel, _rand
@@ -280,8 +280,9 @@ def kv_slot_copy(kv: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, block_s
     """Copy token slots (all layers, K and V) inside a paged cache [L, 2, NB, nkv, bs, hd]:
     every source is read before any destination is written (a compaction chain's source can
     be another move's destination).  GPU: two HIP kernels (kv_ops.hip: gather, scatter)."""
-    if ops._native(kv) and kv.dtype in (torch.bfloat16, torch.float16):
-        torch.ops.dgi.kv_slot_copy(kv, src.to(torch.int32).contiguous(), dst.to(torch.int32).contiguous())
+    if ops._native(kv) and kv.dtype in (torch.bfloat16, torch.float16, ops.KV_FP8):
+        # an fp8 cache moves as 16-bit elements of half the head dim
+        torch.ops.dgi.kv_slot_copy(ops._as16(kv), src.to(torch.int32).contiguous(), dst.to(torch.int32).contiguous())
         return
     L, two, NB, nkv, bs, hd = kv.shape
     c = kv.view(L * two, NB, nkv, bs, hd)
@@ -768,6 +769,7 @@ class SpecEngine(LLMEngine):
 
     def __init__(self, cfg: EngineConfig, spec: Optional[SpecConfig] = None, model_cfg: Optional[ModelConfig] = None,
                  model=None, draft: Optional[Eagle3Draft] = None):
+        refuse_fp8_kv(cfg, "EAGLE-3 speculation")
         super().__init__(cfg, model_cfg, model)
         self.spec = spec or SpecConfig()
         self.spec.validate()

@@ -3,6 +3,12 @@
 * paged prefill (dgi HIP kernel): B prompts of L tokens, causal, KV in the paged pool;
   reference point: torch SDPA (ROCm flash/CK path) on the same dense problem;
 * paged decode (dgi HIP kernel): B sequences at context C; effective KV bandwidth.
+
+Every row also times the same problem on an fp8 KV cache (e4m3 pages, per-head scales): the
+``fp8_*`` columns, with the bytes the fp8 pages actually move.
+
+ATTN_HEADS="32,8" picks another head geometry (nh,nkv); ATTN_PREFILL="8x512,1x8192" and
+ATTN_DECODE="512x576,768x576" pick the (B x L) / (B x C) shapes.
 """
 import json
 import math
@@ -17,7 +23,24 @@ import torch.nn.functional as F
 from dgi import ops
 
 nh, nkv, hd, bs = 64, 8, 128, 16
+if os.environ.get("ATTN_HEADS"):
+    nh, nkv = (int(x) for x in os.environ["ATTN_HEADS"].split(","))
 dev = "cuda"
+
+
+def fp8_pages(kc, vc):
+    """The e4m3 codes of bf16 pages for per-head power-of-two scales, and the scales [2, nkv]."""
+    h = torch.arange(nkv, device=dev)
+    sc = torch.stack([torch.exp2(((h % 3) - 1).float()), torch.exp2((((h + 1) % 3) - 1).float())])
+    inv = 1.0 / sc
+    k8 = ops.quantize_kv_ref(kc.transpose(1, 2), inv[0]).transpose(1, 2).contiguous()
+    v8 = ops.quantize_kv_ref(vc.transpose(1, 2), inv[1]).transpose(1, 2).contiguous()
+    return k8, v8, sc
+
+
+def shapes(env, default):
+    v = os.environ.get(env)
+    return [tuple(int(x) for x in s.split("x")) for s in v.split(",")] if v else default
 
 
 def timed(fn, iters=20):
@@ -46,6 +69,8 @@ def prefill(B, L):
     out = torch.empty(B * L, nh * hd, device=dev, dtype=torch.bfloat16)
     scale = 1 / math.sqrt(hd)
     us = timed(lambda: ops.paged_prefill(q, kc, vc, bt, cu, ctx, nh, nkv, scale, tiles=tiles, out=out))
+    k8, v8, sc = fp8_pages(kc, vc)
+    us8 = timed(lambda: ops.paged_prefill(q, k8, v8, bt, cu, ctx, nh, nkv, scale, tiles=tiles, out=out, kv_scale=sc))
     flops = 4 * nh * hd * B * L * L / 2
     qd = torch.randn(B, nh, L, hd, device=dev, dtype=torch.bfloat16)
     kd = torch.randn(B, nh, L, hd, device=dev, dtype=torch.bfloat16)
@@ -53,7 +78,7 @@ def prefill(B, L):
     us_sdpa = timed(lambda: F.scaled_dot_product_attention(qd, kd, vd, is_causal=True))
     return {"kernel": "prefill", "B": B, "L": L, "tile": ops.PREFILL_TILE, "db": ops.PREFILL_DB,
             "order": os.environ.get("ATTN_TILE_ORDER", "1"), "us": round(us, 1),
-            "TFLOPs": round(flops / us / 1e6, 1),
+            "TFLOPs": round(flops / us / 1e6, 1), "fp8_us": round(us8, 1), "fp8_TFLOPs": round(flops / us8 / 1e6, 1),
             "sdpa_us": round(us_sdpa, 1), "sdpa_TFLOPs": round(flops / us_sdpa / 1e6, 1)}
 
 
@@ -70,18 +95,22 @@ def decode(B, C):
     ws = (torch.empty(B * nh * ((C + 127) // 128) * hd, device=dev), torch.empty(B * nh * ((C + 127) // 128), device=dev))
     scale = 1 / math.sqrt(hd)
     us = timed(lambda: ops.paged_decode(q, kc, vc, bt, ctx, nh, nkv, scale, splits, part, out=out, workspace=ws))
+    k8, v8, sc = fp8_pages(kc, vc)
+    us8 = timed(lambda: ops.paged_decode(q, k8, v8, bt, ctx, nh, nkv, scale, splits, part, out=out, workspace=ws,
+                                         kv_scale=sc))
     byts = B * C * nkv * hd * 2 * 2
-    return {"kernel": "decode", "B": B, "C": C, "splits": splits, "us": round(us, 1),
-            "KV_TBs": round(byts / us / 1e6, 2)}
+    return {"kernel": "decode", "nh": nh, "nkv": nkv, "B": B, "C": C, "splits": splits, "us": round(us, 1),
+            "KV_TBs": round(byts / us / 1e6, 2), "fp8_us": round(us8, 1), "fp8_KV_TBs": round(byts / 2 / us8 / 1e6, 2),
+            "fp8_speedup": round(us / us8, 3)}
 
 
 if __name__ == "__main__":
     for tile in [int(t) for t in os.environ.get("ATTN_TILES", "128").split(",")]:
         for db in [int(d) for d in os.environ.get("ATTN_DB", str(ops.PREFILL_DB)).split(",")]:
             ops.PREFILL_TILE, ops.PREFILL_DB = tile, db
-            for B, L in [(1, 512), (3, 512), (8, 512), (4, 2048), (1, 8192)]:
+            for B, L in shapes("ATTN_PREFILL", [(1, 512), (3, 512), (8, 512), (4, 2048), (1, 8192)]):
                 print(json.dumps(prefill(B, L)), flush=True)
     if os.environ.get("ATTN_PREFILL_ONLY"):
         sys.exit(0)
-    for B, C in [(1, 1024), (64, 1024), (256, 640), (384, 640), (512, 2048), (32, 8192)]:
+    for B, C in shapes("ATTN_DECODE", [(1, 1024), (64, 1024), (256, 640), (384, 640), (512, 2048), (32, 8192)]):
         print(json.dumps(decode(B, C)), flush=True)

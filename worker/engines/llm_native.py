@@ -104,6 +104,14 @@ class NativeLLMEngine(LLMBaseEngine):
             logger.warning("quantization=%r is not supported by the native engine (supported: 'fp8', weight-only); "
                            "serving %s unquantised", quant, model_id)
             quant = None
+        # vLLM / SGLang name it kv_cache_dtype; "auto" and the activation dtypes mean no KV quantisation
+        kvd = c.get("kv_cache_dtype", c.get("kv_dtype"))
+        if kvd is not None and str(kvd).lower() in ("", "none", "auto", "bf16", "bfloat16"):
+            kvd = None
+        if kvd is not None and str(kvd).lower() not in ("fp8", "fp8_e4m3"):
+            logger.warning("kv_cache_dtype=%r is not supported by the native engine (supported: 'fp8', e4m3 pages "
+                           "with per-head scales); serving %s with a bf16 KV cache", kvd, model_id)
+            kvd = None
         frac = c.get("mem_fraction_static", c.get("gpu_memory_utilization", c.get("kv_fraction", 0.9)))
         ecfg = EngineConfig(
             model=model_id, device=device, model_path=ckpt,
@@ -115,6 +123,7 @@ class NativeLLMEngine(LLMBaseEngine):
             use_graphs=bool(c.get("use_graphs", not c.get("enforce_eager", False))) and device != "cpu",
             seed=int(c.get("seed", 0)), block_size=int(c.get("block_size", 16)),
             host_kv_gb=float(c.get("host_kv_gb", 0.0)), weight_quant="fp8" if quant is not None else None,
+            kv_dtype="fp8" if kvd is not None else None,
             graph_buckets=tuple(c["graph_batch_buckets"]) if c.get("graph_batch_buckets") else None)
         spec = c.get("speculative")
         if spec:
@@ -170,8 +179,8 @@ class NativeLLMEngine(LLMBaseEngine):
                     sp = SamplingParams(max_tokens=cfg.max_tokens, temperature=cfg.temperature, top_p=cfg.top_p,
                                         top_k=cfg.top_k)
                     if imported is not None:       # decode phase of a cluster P/D job: KV pulled from its prefill worker
-                        first, kv, seed = imported
-                        p.req = eng.import_prefilled(prompt, first, kv, sp, seed=seed)
+                        first, kv, seed, kv_scale = imported
+                        p.req = eng.import_prefilled(prompt, first, kv, sp, seed=seed, kv_scale=kv_scale)
                         self.stats["kv_imported"] += 1
                         if p.stream_q is not None:
                             p.loop.call_soon_threadsafe(p.stream_q.put_nowait, first)
@@ -236,7 +245,7 @@ class NativeLLMEngine(LLMBaseEngine):
         def pack():
             if ev is not None:
                 ev.synchronize()
-            return pack_kv(host, meta)
+            return pack_kv(host, meta, kv_scale=eng.pool.kv_scale)
         self.kv_exports.put_pending(p.export_key, self._export_pool().submit(pack), token=p.export_token)
         self.stats["kv_exported"] += 1
 
@@ -317,7 +326,7 @@ class NativeLLMEngine(LLMBaseEngine):
 
         async def run():
             return await self._submit(None, cfg, prompt=list(meta["prompt"]),
-                                      imported=(int(meta["first_token"]), kv, seed)).future
+                                      imported=(int(meta["first_token"]), kv, seed, meta.get("kv_scale"))).future
         return result_to_response(self._run_sync(run()))
 
     def _run_sync(self, coro):

@@ -34,6 +34,9 @@ int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, voi
 int dgi_skinny_gemm_w8(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
                        int ldy, int M, int N, int K, int cfg, hipStream_t s);
 int dgi_dequant_fp8(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
+int dgi_quant_rows_fp8(const void* x, int ldx, void* q, void* sx, int M, int K, hipStream_t s);
+int dgi_mfma_gemm_fp8(const void* xq, const void* sx, const void* wq, const void* sw, const void* bias, void* y,
+                      int ldy, int M, int N, int K, hipStream_t s);
 int dgi_mfma_gemm(const void* x, int ldx, const void* w, void* y, int ldy, int M, int N, int K, int swiglu,
                   int sched, int streamk, int phases, int overlap, hipStream_t s);
 int dgi_gemm_split_timeouts(int reset);
@@ -299,6 +302,67 @@ void dequant_fp8(at::Tensor out, const at::Tensor& wq, const at::Tensor& scale) 
   check_rc(dgi_dequant_fp8(wq.data_ptr(), scale.data_ptr(), out.data_ptr(), (int)wq.size(0), (int)wq.size(1),
                            cur_stream()),
            "dequant_fp8");
+}
+
+// W8A8 row quantiser: q [M, K] e4m3 and sx [M] fp32 from x [M, K] bf16 (rows may be strided):
+// sx = max|x[m]| / 448 (1 for a zero row), q = rne_e4m3(x * (448 / max|x[m]|)).
+void quant_rows_fp8(at::Tensor q, at::Tensor sx, const at::Tensor& x) {
+  check_bf16(x, "x"); check_dev(q, "q"); check_dev(sx, "sx");
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn, "quant_rows_fp8: q must be float8_e4m3fn");
+  TORCH_CHECK(sx.scalar_type() == at::kFloat, "quant_rows_fp8: sx must be float32");
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 2 && q.size(0) == x.size(0) && q.size(1) == x.size(1),
+              "quant_rows_fp8: x and q are [M, K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(q.is_contiguous() && sx.is_contiguous() && sx.numel() == M,
+              "quant_rows_fp8: contiguous q, one scale per row");
+  TORCH_CHECK(x.device() == q.device() && x.device() == sx.device(), "quant_rows_fp8: operands on one device");
+  TORCH_CHECK((K <= 1 || x.stride(1) == 1) && (M <= 1 || x.stride(0) >= K), "quant_rows_fp8: row-major x");
+  const int64_t ldx = M > 1 ? x.stride(0) : K;
+  TORCH_CHECK(K % 16 == 0 && ldx % 8 == 0 && M < (1LL << 31) && ldx < (1LL << 31) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "quant_rows_fp8: K%16, row stride%8, 16-byte aligned x and q");
+  check_rc(dgi_quant_rows_fp8(x.data_ptr(), (int)ldx, q.data_ptr(), sx.data_ptr(), (int)M, (int)K, cur_stream()),
+           "quant_rows_fp8");
+}
+
+// W8A8 GEMM: out = (xq wq^T) * sx[:, None] * sw[None, :] (+ bias); xq [M, K] and wq [N, K] OCP e4m3,
+// sx [M] and sw [N] fp32 (per token, per output channel).
+void mfma_gemm_fp8(at::Tensor out, const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& wq,
+                   const at::Tensor& sw, const c10::optional<at::Tensor>& bias) {
+  check_bf16(out, "out"); check_dev(xq, "xq"); check_dev(sx, "sx"); check_dev(wq, "wq"); check_dev(sw, "sw");
+  TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn && wq.scalar_type() == at::kFloat8_e4m3fn,
+              "mfma_gemm_fp8: xq and wq must be float8_e4m3fn");
+  TORCH_CHECK(sx.scalar_type() == at::kFloat && sw.scalar_type() == at::kFloat,
+              "mfma_gemm_fp8: sx and sw must be float32");
+  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && out.dim() == 2, "mfma_gemm_fp8: 2-D operands");
+  TORCH_CHECK(xq.is_contiguous() && wq.is_contiguous() && sx.is_contiguous() && sw.is_contiguous() &&
+                  out.stride(1) == 1,
+              "mfma_gemm_fp8: contiguous xq, wq and scales, row-major out");
+  TORCH_CHECK(xq.device() == wq.device() && xq.device() == out.device() && xq.device() == sx.device() &&
+                  xq.device() == sw.device(),
+              "mfma_gemm_fp8: operands on one device");
+  const int64_t M = xq.size(0), K = xq.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K && out.size(0) == M && out.size(1) == N && sx.numel() == M && sw.numel() == N,
+              "mfma_gemm_fp8: shape mismatch");
+  const int64_t ldy = M > 1 ? out.stride(0) : N;
+  TORCH_CHECK(M >= 1 && N % 256 == 0 && K >= 128 && K % 128 == 0 && ldy >= N && ldy % 4 == 0 &&
+                  ldy < (1LL << 31) && M * K < (1LL << 31) && N * K < (1LL << 31) &&
+                  reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(sw.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "mfma_gemm_fp8: M>=1, N%256, K%128, out row stride%4, operands below 2 GB, 16-byte aligned xq, wq, sw");
+  const void* b = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == out.device() &&
+                reinterpret_cast<uintptr_t>(bias->data_ptr()) % 8 == 0);
+    b = bias->data_ptr();
+  }
+  check_rc(dgi_mfma_gemm_fp8(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), b, out.data_ptr(), (int)ldy,
+                             (int)M, (int)N, (int)K, cur_stream()),
+           "mfma_gemm_fp8");
 }
 
 // LDS-tiled MFMA GEMM (prefill / mixed steps): epi 0 out = x w^T; epi 1 out = SwiGLU with w = [gate; up].
@@ -674,6 +738,8 @@ TORCH_LIBRARY(dgi, m) {
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
   m.def("skinny_gemm_w8(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");
   m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
+  m.def("quant_rows_fp8(Tensor(a!) q, Tensor(b!) sx, Tensor x) -> ()");
+  m.def("mfma_gemm_fp8(Tensor(a!) out, Tensor xq, Tensor sx, Tensor wq, Tensor sw, Tensor? bias) -> ()");
   m.def("mfma_gemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, int sched=3, int streamk=0, int phases=0, "
         "bool overlap=True) -> ()");
   m.def("mfma_gemm_norm(Tensor(a!) out, Tensor x, Tensor w, int kind, Tensor(b!) ss, float inv_k, float eps, "
@@ -710,6 +776,8 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("skinny_gemm_w8", &skinny_gemm_w8);
   m.impl("dequant_fp8", &dequant_fp8);
+  m.impl("quant_rows_fp8", &quant_rows_fp8);
+  m.impl("mfma_gemm_fp8", &mfma_gemm_fp8);
   m.impl("mfma_gemm", &mfma_gemm);
   m.impl("mfma_gemm_norm", &mfma_gemm_norm);
   m.impl("mfma_gemm_norm_rope", &mfma_gemm_norm_rope);

@@ -61,6 +61,26 @@ __device__ __forceinline__ bf16x8 as_bf16x8(const u32x4& v) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// The 256 x 256 GEMM tiles (mfma_gemm.hip, mfma_gemm_fp8.hip): a lane holds rows
+// m0 + 128 wm + 16 i + (lane & 15), columns 4 (lane >> 4) + 0..3 of each 16x16 tile.
+// Two neighbouring tiles (A, B) are stored as ONE 16-byte store per lane: v_permlane16_swap
+// trades A's columns of the odd 16-lane rows for B's columns of the even rows, so lane group
+// g ends up with 8 consecutive columns — A 0-7 (g 0), B 0-7 (g 1), A 8-15 (g 2), B 8-15 (g 3) —
+// and every row of a store instruction writes 64 contiguous bytes (half the store
+// instructions of 8-byte stores; the store tail of a tile's epilogue is issue-bound).
+__device__ __forceinline__ void store_pair16(uint16_t* yrow, int n0, int g, const float (&a)[4], const float (&b)[4]) {
+  const uint32_t a01 = pack_bf16x2(a[0], a[1]), a23 = pack_bf16x2(a[2], a[3]);
+  const uint32_t b01 = pack_bf16x2(b[0], b[1]), b23 = pack_bf16x2(b[2], b[3]);
+  const auto s0 = __builtin_amdgcn_permlane16_swap(a01, b01, false, false);
+  const auto s1 = __builtin_amdgcn_permlane16_swap(a23, b23, false, false);
+  uint4 v;
+  v.x = s0[0];
+  v.y = s1[0];
+  v.z = s0[1];
+  v.w = s1[1];
+  *(uint4*)(yrow + n0 + 16 * (g & 1) + 4 * (g & 2)) = v;
+}
+
 // ---- e4m3 (OCP float8_e4m3fn) helpers: W8A16 weights and the fp8 KV cache.
 // Two e4m3 codes of `word` (low or high half) -> two bf16 in one word.
 __device__ __forceinline__ uint32_t widen2(uint32_t word, bool hi) {

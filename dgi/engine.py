@@ -26,6 +26,7 @@ from dgi.utils.trace import phase
 
 
 WEIGHT_QUANT_MODES = (None, "fp8")
+ACT_QUANT_MODES = (None, "fp8")       # "fp8": W8A8 on top of weight_quant="fp8"
 KV_DTYPES = (None, "fp8")      # None: KV pages in the activation dtype; "fp8": e4m3 codes + per-head scales
 logger = logging.getLogger(__name__)
 
@@ -73,6 +74,9 @@ class EngineConfig:
     decode_lookahead: bool = True      # pure-decode graph steps: launch step N+1 before step N's
                                        # tokens are back (``LLMEngine._lookahead``); DGI_DECODE_LOOKAHEAD=0
     weight_quant: Optional[str] = None   # "fp8": weight-only e4m3 projections (``LlamaModel.quantize_weights``)
+    act_quant: Optional[str] = None      # "fp8" (with weight_quant="fp8"): W8A8 — per-token e4m3 activations and the
+                                         # e4m3 GEMM for steps of >= ops.W8A8_MIN_M rows (a token's numerics then
+                                         # depend on its step's row count)
     kv_dtype: Optional[str] = None       # "fp8": e4m3 KV pages with per-head scales (``BlockPool.kv_scale``)
 
     def __post_init__(self):
@@ -82,6 +86,11 @@ class EngineConfig:
         if self.weight_quant not in WEIGHT_QUANT_MODES:
             raise ValueError(f"EngineConfig.weight_quant={self.weight_quant!r}: supported values are "
                              f"{', '.join(repr(m) for m in WEIGHT_QUANT_MODES)}")
+        if self.act_quant not in ACT_QUANT_MODES:
+            raise ValueError(f"EngineConfig.act_quant={self.act_quant!r}: supported values are "
+                             f"{', '.join(repr(m) for m in ACT_QUANT_MODES)}")
+        if self.act_quant == "fp8" and self.weight_quant != "fp8":
+            raise ValueError("EngineConfig.act_quant='fp8' needs weight_quant='fp8' (W8A8 runs on the fp8 weights)")
 
 
 @dataclasses.dataclass
@@ -154,9 +163,10 @@ class LLMEngine:
         t0 = time.perf_counter()
         self.model = model or LlamaModel(self.model_cfg, self.device, cfg.dtype, cfg.layer_start, cfg.layer_end,
                                          seed=cfg.seed, checkpoint=self.checkpoint)
-        if cfg.weight_quant and getattr(self.model, "weight_quant", None) != cfg.weight_quant:
+        if cfg.weight_quant and (getattr(self.model, "weight_quant", None) != cfg.weight_quant
+                                 or getattr(self.model, "act_quant", None) != cfg.act_quant):
             # before the KV budget: the pool gets the HBM the bf16 projections give back
-            self.model.quantize_weights(cfg.weight_quant)
+            self.model.quantize_weights(cfg.weight_quant, act_quant=cfg.act_quant)
         if self.device.type == "cuda":
             torch.cuda.synchronize()
         self.load_seconds = time.perf_counter() - t0

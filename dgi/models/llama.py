@@ -143,6 +143,7 @@ class LlamaModel:
         self.fold_impl = None        # rows -> run the fused-norm layers? (dgi.runtime.gemm_pad)
         self._ss_buf: Optional[torch.Tensor] = None
         self.weight_quant: Optional[str] = None     # "fp8": the four projections per layer are ops.Fp8Weight
+        self.act_quant: Optional[str] = None        # "fp8": W8A8 above ops.W8A8_MIN_M rows (quantize_weights)
         self._quant_scratch: Optional[torch.Tensor] = None
         if checkpoint:
             # real weights: only this rank's layers / TP slices are read (dgi.models.weights)
@@ -232,14 +233,21 @@ class LlamaModel:
                                            dtype=torch.float32)
         self.norms_folded = True
 
-    def quantize_weights(self, mode: str = "fp8") -> "LlamaModel":
+    def quantize_weights(self, mode: str = "fp8", act_quant: Optional[str] = None) -> "LlamaModel":
         """Weight-only quantisation of each layer's qkv / o / gate_up / down projection
         (``ops.quantize_fp8``: e4m3 codes, one fp32 scale per output channel), one layer at a
         time, dropping the bf16 tensor as it goes.  Norm gains, ``qkv_bias``, ``embed`` and
-        ``lm_head`` keep their dtype.  Steps then run ``_forward_layers_quant``."""
+        ``lm_head`` keep their dtype.  Steps then run ``_forward_layers_quant``.
+
+        ``act_quant="fp8"`` (W8A8) marks every quantised projection so that steps of at least
+        ``ops.W8A8_MIN_M`` rows quantise their activations per token and run the e4m3 GEMM
+        (``ops.linear_w8a8``); smaller steps stay W8A16."""
         if mode != "fp8":
             raise ValueError(f"quantize_weights: unsupported mode {mode!r} (supported: 'fp8')")
+        if act_quant not in (None, "fp8"):
+            raise ValueError(f"quantize_weights: unsupported act_quant {act_quant!r} (supported: None, 'fp8')")
         if self.weight_quant == mode:
+            self._set_act_quant(act_quant)
             return self
         largest = 0
         for L in self.layers:
@@ -257,10 +265,17 @@ class LlamaModel:
                 for k in QUANT_SLOTS:
                     getattr(L, k).scratch = self._quant_scratch
         self.weight_quant = mode
+        self._set_act_quant(act_quant)
         if self.device.type == "cuda":
             # the KV budget reads driver-free memory: hand the freed bf16 blocks back to the driver
             torch.cuda.empty_cache()
         return self
+
+    def _set_act_quant(self, act_quant: Optional[str]) -> None:
+        for L in self.layers:
+            for k in QUANT_SLOTS:
+                getattr(L, k).act = act_quant
+        self.act_quant = act_quant
 
     def _check_not_quantised(self, what: str) -> None:
         if self.weight_quant:
@@ -321,6 +336,9 @@ class LlamaModel:
         if self.weight_quant != other.weight_quant:
             raise RuntimeError(f"copy_from: this model's weights are {self.weight_quant or 'unquantised'}, the "
                                f"source's {other.weight_quant or 'unquantised'}; copy first, then quantize_weights")
+        if self.act_quant != other.act_quant:
+            raise RuntimeError(f"copy_from: this model's act_quant is {self.act_quant!r}, the source's "
+                               f"{other.act_quant!r}; quantize_weights both with the same act_quant")
         src = dict(other.tensors())
         self.norms_folded = other.norms_folded
         for name, t in self.tensors():

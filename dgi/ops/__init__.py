@@ -19,7 +19,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from dgi.ops.fp8 import Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
+from dgi.ops.fp8 import E4M3_MAX, Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
 
 _LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_C.so")
 _loaded = False
@@ -540,10 +540,98 @@ def dequant_fp8(w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tenso
     return out
 
 
+# FP8 W8A8 projections (mfma_gemm_fp8.hip): an opt-in mode on top of the fp8 weights
+# (Fp8Weight.act == "fp8").  Steps of at least W8A8_MIN_M rows quantise their activations per
+# token (quant_rows_fp8) and multiply e4m3 by e4m3 on the block-scaled MFMA (mfma_gemm_fp8);
+# smaller steps keep the W8A16 order below.  A token's numerics therefore depend on the row count
+# of the step it runs in.  Default 2048: the smallest measured row count from which quantiser +
+# e4m3 GEMM beat dequantise + bf16 GEMM on every Llama-3-8B / 70B projection (the e4m3 kernel has
+# one schedule and no split-K, so short steps of the narrow projections lose;
+# profiles/w8a8/README.md has the per-shape crossovers: 64 rows for gate_up, 256 for all of 70B).
+W8A8_MIN_M = int(os.environ.get("DGI_W8A8_MIN_M", "2048"))
+
+
+def quant_rows_fp8_ref(x: torch.Tensor):
+    """Per-row dynamic e4m3 quantisation of a [M, K] activation, in fp32: ``sx = max|x| / 448`` and
+    ``q = rne_e4m3(clamp(x * (448 / max|x|), -448, 448))``; a zero row takes ``sx = 1``."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=1)
+    one = torch.ones_like(amax)
+    # tensor / tensor: IEEE divisions (torch turns ``scalar / tensor`` into reciprocal * scalar, and
+    # on the GPU ``tensor / scalar`` too — one ulp off often enough to move a code across a tie)
+    top = torch.full_like(amax, E4M3_MAX)
+    sx = torch.where(amax > 0, amax / top, one)
+    inv = torch.where(amax > 0, top / amax, one)
+    q = (xf * inv[:, None]).clamp_(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q, sx
+
+
+def _quant_rows_native(x: torch.Tensor) -> bool:
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] % 16 == 0
+            and (x.shape[1] <= 1 or x.stride(1) == 1)
+            and (x.shape[0] <= 1 or (x.stride(0) >= x.shape[1] and x.stride(0) % 8 == 0))
+            and x.data_ptr() % 16 == 0)
+
+
+def quant_rows_fp8(x: torch.Tensor):
+    """``(q, sx)`` of a [M, K] activation: the kernel for bf16 GPU rows, the reference elsewhere."""
+    if _quant_rows_native(x):
+        load_native(required=True)
+        q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+        sx = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        _call("quant_rows_fp8", q, sx, x)
+        return q, sx
+    return quant_rows_fp8_ref(x)
+
+
+def linear_w8a8_ref(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    q, sx = quant_rows_fp8_ref(x)
+    r = (q.float() @ w.q.float().T) * sx[:, None] * w.scale[None, :]
+    if bias is not None:
+        r = r + bias.float()
+    return r.to(x.dtype)
+
+
+def _w8a8_fits(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor] = None) -> bool:
+    """Whether quant_rows_fp8 + mfma_gemm_fp8 take this activation, weight and bias: shapes, sizes
+    and the alignment of their 16-byte (bias: 8-byte) accesses."""
+    N, K = w.shape
+    return (x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] == K and _quant_rows_native(x)
+            and N % 256 == 0 and K % 128 == 0 and K >= 128 and N * K < (1 << 31) and x.shape[0] * K < (1 << 31)
+            and w.q.data_ptr() % 16 == 0 and w.scale.data_ptr() % 16 == 0
+            and (bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous() and bias.data_ptr() % 8 == 0)))
+
+
+def linear_w8a8(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W8A8 projection of a 2-D activation: quantiser + e4m3 GEMM where the kernels' requirements
+    hold, ``linear_w8a8_ref`` otherwise."""
+    N = w.shape[0]
+    if _w8a8_fits(x, w, bias):
+        M = x.shape[0]
+        direct = (out is not None and out.dtype == torch.bfloat16 and out.shape == (M, N) and out.is_cuda
+                  and out.stride(1) == 1 and (M == 1 or (out.stride(0) >= N and out.stride(0) % 4 == 0))
+                  and out.data_ptr() % 8 == 0)
+        r = out if direct else torch.empty(M, N, dtype=x.dtype, device=x.device)
+        q, sx = quant_rows_fp8(x)
+        _call("mfma_gemm_fp8", r, q, sx, w.q, w.scale, bias)
+        if direct:
+            return out
+    else:
+        r = linear_w8a8_ref(x, w, bias)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
 def _linear_fp8(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor], out: Optional[torch.Tensor]):
+    w8a8 = w.act == "fp8" and x.dim() == 2 and x.shape[0] >= W8A8_MIN_M
     if x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16:
         M, K = x.shape
         N = w.shape[0]
+        if w8a8 and _w8a8_fits(x, w, bias):
+            return linear_w8a8(x, w, bias, out)
         if _use_skinny_w8(M, N, K) and x.stride(1) == 1 and x.stride(0) % 8 == 0:
             load_native(required=True)
             if out is None:
@@ -551,6 +639,8 @@ def _linear_fp8(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor], out
             _call("skinny_gemm_w8", out, x, w.q, w.scale, bias, _skinny_w8_cfg(M, N))
             return out
         r = torch.nn.functional.linear(x, dequant_fp8(w, w.scratch), bias)
+    elif w8a8:
+        r = linear_w8a8_ref(x, w, bias)
     else:
         r = linear_fp8_ref(x, w, bias)
     if out is not None:

@@ -16,9 +16,10 @@ E4M3_MAX = 448.0
 
 class Fp8Weight:
     """``q`` [N, K] e4m3 codes, ``scale`` [N] fp32: the weight is ``q * scale[:, None]``."""
-    __slots__ = ("q", "scale", "scratch")
+    __slots__ = ("q", "scale", "scratch", "act")
 
-    def __init__(self, q: torch.Tensor, scale: torch.Tensor, scratch: Optional[torch.Tensor] = None):
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor, scratch: Optional[torch.Tensor] = None,
+                 act: Optional[str] = None):
         if q.dtype != torch.float8_e4m3fn or q.dim() != 2 or not q.is_contiguous():
             raise ValueError("Fp8Weight: q must be a contiguous [N, K] float8_e4m3fn tensor")
         if scale.dtype != torch.float32 or scale.shape != (q.shape[0],) or not scale.is_contiguous():
@@ -28,6 +29,11 @@ class Fp8Weight:
         # flat bf16 buffer of >= N*K elements the dequantised copy is written to for the shapes
         # the fp8 kernel does not take (shared by every layer of a model); None: allocated per call
         self.scratch = scratch
+        if act not in (None, "fp8"):
+            raise ValueError("Fp8Weight: act must be None or 'fp8'")
+        # "fp8": W8A8 — steps of at least ops.W8A8_MIN_M rows quantise their activations per
+        # token to e4m3 and run the e4m3 GEMM; None: W8A16 at every row count
+        self.act = act
 
     @property
     def shape(self) -> torch.Size:

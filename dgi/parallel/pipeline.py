@@ -277,7 +277,7 @@ class PipelineEngine(LLMEngine):
         model = LlamaModel(mc, device, cfg.dtype, a, b, has_embed=True, has_head=len(self.ranks) == 1, seed=cfg.seed,
                            checkpoint=ckpt)
         if cfg.weight_quant:        # before the page budget, like LLMEngine
-            model.quantize_weights(cfg.weight_quant)
+            model.quantize_weights(cfg.weight_quant, act_quant=cfg.act_quant)
         nb = stage_block_budget(mc, device, b - a, cfg)
         nb = agree_num_blocks(fabric, self.ranks, nb)
         pcfg = EngineConfig(**{**cfg.__dict__, "device": str(device), "layer_start": a, "layer_end": b,
@@ -537,7 +537,7 @@ class StageWorker:
         self.model = LlamaModel(mc, dev, cfg.dtype, a, b, has_embed=False, has_head=self.is_last, seed=cfg.seed,
                                 checkpoint=ckpt)
         if cfg.weight_quant:        # every stage serves the same weight format
-            self.model.quantize_weights(cfg.weight_quant)
+            self.model.quantize_weights(cfg.weight_quant, act_quant=cfg.act_quant)
         nb = stage_block_budget(mc, dev, b - a, cfg)
         nb = agree_num_blocks(fabric, self.ranks, nb)
         self.pool = BlockPool(nb, cfg.block_size, b - a, mc.num_kv_heads, mc.head_dim, cfg.dtype, dev)

@@ -111,7 +111,7 @@ class TPEngine(LLMEngine):
         model = TPLlamaModel(full, dev, cfg.dtype, tp_rank, tp, group, seed=cfg.seed, checkpoint=ckpt)
         cfg = dataclasses.replace(cfg, device=str(dev))
         if cfg.weight_quant:        # before the page budget, like LLMEngine
-            model.quantize_weights(cfg.weight_quant)
+            model.quantize_weights(cfg.weight_quant, act_quant=cfg.act_quant)
         if tp > 1:
             # every rank must hold the same page count (block ids are shared): agree on the minimum
             nb = engine_block_budget(cfg, model.cfg, model.num_local_layers, dev)

@@ -101,7 +101,7 @@ class Router:
         cfg = EngineConfig(model=args.model, device=dev, max_num_seqs=args.max_num_seqs,
                            max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                            use_graphs=dev.startswith("cuda") and not args.no_graphs, seed=args.seed,
-                       weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
+                           weight_quant=args.weight_quant, act_quant=args.act_quant, kv_dtype=args.kv_dtype)
         self.drv = None
         self.chans = {}
         self.load = collections.Counter()
@@ -337,7 +337,7 @@ def _prefill_loop(args, fabric, layout) -> None:
     cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=64 + cap,
                        max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                        use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed,
-                       weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
+                       weight_quant=args.weight_quant, act_quant=args.act_quant, kv_dtype=args.kv_dtype)
     srv = PrefillServer(cfg, fabric, layout, local_cap=cap, report_tokens=True)
     inbox = CtrlChannel(fabric, layout.drivers[0], 1, tag="req")
     stopping = False
@@ -368,7 +368,7 @@ def _replica_loop(args, fabric, layout) -> None:
     cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=args.max_num_seqs,
                        max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                        use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs, seed=args.seed,
-                       weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
+                       weight_quant=args.weight_quant, act_quant=args.act_quant, kv_dtype=args.kv_dtype)
     drv = DecodeDriver(cfg, fabric, layout)
     drv.track_arrivals = True
     drv.forward_tokens = True
@@ -402,6 +402,9 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weight-quant", default=None, choices=["fp8"],
                     help="weight-only quantisation of the layer projections (default: bf16 weights)")
+    ap.add_argument("--act-quant", default=None, choices=["fp8"],
+                    help="with --weight-quant fp8: W8A8, per-token e4m3 activations and the e4m3 GEMM for steps of "
+                         "at least DGI_W8A8_MIN_M rows, 2048 unless set (default: bf16 activations at every step size)")
     ap.add_argument("--kv-dtype", default=None, choices=["fp8"],
                     help="KV cache pages as e4m3 codes with per-head scales (default: bf16 pages); "
                          "single-GPU engines only")
@@ -431,7 +434,8 @@ def main(argv=None) -> int:
             cfg = EngineConfig(model=args.model, device=str(fabric.device), max_num_seqs=args.max_num_seqs,
                                max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                                use_graphs=str(fabric.device).startswith("cuda") and not args.no_graphs,
-                               seed=args.seed, enable_prefix_caching=False, weight_quant=args.weight_quant, kv_dtype=args.kv_dtype)
+                               seed=args.seed, enable_prefix_caching=False, weight_quant=args.weight_quant,
+                               act_quant=args.act_quant, kv_dtype=args.kv_dtype)
             w = StageWorker(cfg, fabric, layout.group_of(fabric.rank), kv_sources=layout.prefill_ranks)
             while w.run() != "stop":
                 pass

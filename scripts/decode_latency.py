@@ -25,14 +25,19 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--weight-quant", default=None, choices=["fp8"], help="weight-only quantised projections")
+    ap.add_argument("--act-quant", default=None, choices=["fp8"],
+                    help="with --weight-quant fp8: W8A8 for steps of at least DGI_W8A8_MIN_M rows (default 2048)")
+    ap.add_argument("--prefill-tokens", type=int, default=0,
+                    help="also time one prefill step of this many tokens (one prompt, after the decode batches)")
     ap.add_argument("--kv-dtype", default=None, choices=["fp8"], help="fp8 (e4m3) KV cache pages")
     ap.add_argument("--num-blocks", type=int, default=None, help="KV pages (default: from free memory)")
     a = ap.parse_args()
     cfg = EngineConfig(model=a.model, device="cuda", max_num_seqs=max(a.batch), max_num_batched_tokens=8192,
-                       max_model_len=2048, kv_fraction=0.5, weight_quant=a.weight_quant,
+                       max_model_len=max(2048, a.prefill_tokens + 64), kv_fraction=0.5, weight_quant=a.weight_quant,
+                       act_quant=a.act_quant,
                        kv_dtype=a.kv_dtype, num_blocks=a.num_blocks)
     eng = LLMEngine(cfg)
-    print(json.dumps({"model": a.model, "weight_quant": a.weight_quant, "kv_dtype": a.kv_dtype, "weight_bytes": eng.model.weight_bytes(),
+    print(json.dumps({"model": a.model, "weight_quant": a.weight_quant, "act_quant": a.act_quant, "kv_dtype": a.kv_dtype, "weight_bytes": eng.model.weight_bytes(),
                       "num_blocks": eng.pool.num_blocks}), flush=True)
     eng.warmup()
     g = torch.Generator().manual_seed(0)
@@ -58,8 +63,25 @@ def main():
         while eng.has_unfinished():
             eng.step()
         rows.append({"model": a.model, "batch": B, "tpot_ms": round(ms, 3), "tok_s": round(B / ms * 1000, 1), "weight_quant": a.weight_quant,
-                     "kv_dtype": a.kv_dtype,
+                     "act_quant": a.act_quant, "kv_dtype": a.kv_dtype,
                      "skinny_max_m": int(os.environ.get("DGI_SKINNY_MAX_M", "32")), "host_phases_ms": ph})
+        print(json.dumps(rows[-1]), flush=True)
+    if a.prefill_tokens > 0:
+        # one prompt of --prefill-tokens tokens: its first step is a pure prefill of that many rows
+        # (two untimed ones first: lazy allocations and workspace growth)
+        sp = SamplingParams(max_tokens=1, temperature=0.0, ignore_eos=True)
+        times = []
+        for _ in range(5):
+            eng.add_request(torch.randint(1000, V - 1000, (a.prefill_tokens,), generator=g).tolist(), sp)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.step()
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1000)
+            while eng.has_unfinished():
+                eng.step()
+        rows.append({"model": a.model, "prefill_tokens": a.prefill_tokens, "prefill_ms": [round(t, 3) for t in times[2:]],
+                     "weight_quant": a.weight_quant, "act_quant": a.act_quant})
         print(json.dumps(rows[-1]), flush=True)
     if a.out:
         with open(a.out, "w") as f:

@@ -34,6 +34,9 @@ int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, voi
 int dgi_skinny_gemm_w8(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
                        int ldy, int M, int N, int K, int cfg, hipStream_t s);
 int dgi_dequant_fp8(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
+int dgi_skinny_gemm_w4(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
+                       int ldy, int M, int N, int K, int cfg, hipStream_t s);
+int dgi_dequant_mxfp4(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
 int dgi_quant_rows_fp8(const void* x, int ldx, void* q, void* sx, int M, int K, hipStream_t s);
 int dgi_mfma_gemm_fp8(const void* xq, const void* sx, const void* wq, const void* sw, const void* bias, void* y,
                       int ldy, int M, int N, int K, hipStream_t s);
@@ -302,6 +305,59 @@ void dequant_fp8(at::Tensor out, const at::Tensor& wq, const at::Tensor& scale) 
   check_rc(dgi_dequant_fp8(wq.data_ptr(), scale.data_ptr(), out.data_ptr(), (int)wq.size(0), (int)wq.size(1),
                            cur_stream()),
            "dequant_fp8");
+}
+
+// W4A16 decode GEMM over MXFP4 weights: out = x w^T (+ bias); q [N, K/2] bytes of two e2m1 codes (low nibble
+// first), scale [N, K/32] e8m0 bytes, one per 32 elements of a row.
+void skinny_gemm_w4(at::Tensor out, const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale,
+                    const c10::optional<at::Tensor>& bias, int64_t cfg) {
+  check_bf16(out, "out"); check_bf16(x, "x"); check_dev(q, "q"); check_dev(scale, "scale");
+  TORCH_CHECK(q.scalar_type() == at::kByte, "skinny_gemm_w4: q must be uint8");
+  TORCH_CHECK(scale.scalar_type() == at::kByte, "skinny_gemm_w4: scale must be uint8 (e8m0)");
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 2 && scale.dim() == 2 && out.dim() == 2, "skinny_gemm_w4: 2-D operands");
+  TORCH_CHECK(x.stride(1) == 1 && out.stride(1) == 1 && q.is_contiguous() && scale.is_contiguous(),
+              "skinny_gemm_w4: row-major operands");
+  TORCH_CHECK(x.device() == q.device() && x.device() == out.device() && x.device() == scale.device(),
+              "skinny_gemm_w4: operands on one device");
+  const int64_t M = x.size(0), K = x.size(1), N = q.size(0);
+  TORCH_CHECK(M <= 32 && K % 1024 == 0 && N % 16 == 0 && x.stride(0) % 8 == 0,
+              "skinny_gemm_w4: M<=32, K%1024, N%16");
+  TORCH_CHECK(q.size(1) == K / 2 && scale.size(0) == N && scale.size(1) == K / 32 && out.size(0) == M &&
+                  out.size(1) == N,
+              "skinny_gemm_w4: shape mismatch");
+  TORCH_CHECK((M <= 1 || x.stride(0) >= K) && (M <= 1 || out.stride(0) >= N), "skinny_gemm_w4: overlapping rows");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)q.data_ptr() % 16 == 0 &&
+                  (uintptr_t)scale.data_ptr() % 2 == 0,
+              "skinny_gemm_w4: x and q 16-byte aligned, scale 2-byte aligned");
+  const void* b = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == x.device());
+    b = bias->data_ptr();
+  }
+  check_rc(dgi_skinny_gemm_w4(x.data_ptr(), (int)x.stride(0), q.data_ptr(), scale.data_ptr(), b, out.data_ptr(),
+                              (int)out.stride(0), (int)M, (int)N, (int)K, (int)cfg, cur_stream()),
+           "skinny_gemm_w4");
+}
+
+// out [N, K] bf16 = the decoded MXFP4 weight, exactly (the route of every shape skinny_gemm_w4 does not take)
+void dequant_mxfp4(at::Tensor out, const at::Tensor& q, const at::Tensor& scale) {
+  check_bf16(out, "out"); check_dev(q, "q"); check_dev(scale, "scale");
+  TORCH_CHECK(q.scalar_type() == at::kByte, "dequant_mxfp4: q must be uint8");
+  TORCH_CHECK(scale.scalar_type() == at::kByte, "dequant_mxfp4: scale must be uint8 (e8m0)");
+  TORCH_CHECK(q.dim() == 2 && scale.dim() == 2 && out.dim() == 2 && out.size(0) == q.size(0) &&
+                  out.size(1) == 2 * q.size(1),
+              "dequant_mxfp4: out is [N, K], q [N, K/2]");
+  TORCH_CHECK(out.size(1) % 32 == 0 && q.size(0) < (1LL << 31) && out.size(1) < (1LL << 31), "dequant_mxfp4: K%32");
+  TORCH_CHECK(q.is_contiguous() && out.is_contiguous() && scale.is_contiguous() && scale.size(0) == q.size(0) &&
+                  scale.size(1) == out.size(1) / 32,
+              "dequant_mxfp4: contiguous operands, scale [N, K/32]");
+  TORCH_CHECK(out.device() == q.device() && out.device() == scale.device(), "dequant_mxfp4: operands on one device");
+  TORCH_CHECK((uintptr_t)q.data_ptr() % 16 == 0 && (uintptr_t)out.data_ptr() % 16 == 0,
+              "dequant_mxfp4: q and out 16-byte aligned");
+  check_rc(dgi_dequant_mxfp4(q.data_ptr(), scale.data_ptr(), out.data_ptr(), (int)q.size(0), (int)out.size(1),
+                             cur_stream()),
+           "dequant_mxfp4");
 }
 
 // W8A8 row quantiser: q [M, K] e4m3 and sx [M] fp32 from x [M, K] bf16 (rows may be strided):
@@ -738,6 +794,8 @@ TORCH_LIBRARY(dgi, m) {
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
   m.def("skinny_gemm_w8(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");
   m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
+  m.def("skinny_gemm_w4(Tensor(a!) out, Tensor x, Tensor q, Tensor scale, Tensor? bias, int cfg=0) -> ()");
+  m.def("dequant_mxfp4(Tensor(a!) out, Tensor q, Tensor scale) -> ()");
   m.def("quant_rows_fp8(Tensor(a!) q, Tensor(b!) sx, Tensor x) -> ()");
   m.def("mfma_gemm_fp8(Tensor(a!) out, Tensor xq, Tensor sx, Tensor wq, Tensor sw, Tensor? bias) -> ()");
   m.def("mfma_gemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, int sched=3, int streamk=0, int phases=0, "
@@ -776,6 +834,8 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("skinny_gemm_w8", &skinny_gemm_w8);
   m.impl("dequant_fp8", &dequant_fp8);
+  m.impl("skinny_gemm_w4", &skinny_gemm_w4);
+  m.impl("dequant_mxfp4", &dequant_mxfp4);
   m.impl("quant_rows_fp8", &quant_rows_fp8);
   m.impl("mfma_gemm_fp8", &mfma_gemm_fp8);
   m.impl("mfma_gemm", &mfma_gemm);

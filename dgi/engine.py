@@ -25,7 +25,7 @@ from dgi.sched.scheduler import Scheduler, SchedulerConfig
 from dgi.utils.trace import phase
 
 
-WEIGHT_QUANT_MODES = (None, "fp8")
+WEIGHT_QUANT_MODES = (None, "fp8", "mxfp4")
 ACT_QUANT_MODES = (None, "fp8")       # "fp8": W8A8 on top of weight_quant="fp8"
 KV_DTYPES = (None, "fp8")      # None: KV pages in the activation dtype; "fp8": e4m3 codes + per-head scales
 logger = logging.getLogger(__name__)
@@ -73,7 +73,8 @@ class EngineConfig:
                                        # stays under this (dgi.sched.slo.StepBudget)
     decode_lookahead: bool = True      # pure-decode graph steps: launch step N+1 before step N's
                                        # tokens are back (``LLMEngine._lookahead``); DGI_DECODE_LOOKAHEAD=0
-    weight_quant: Optional[str] = None   # "fp8": weight-only e4m3 projections (``LlamaModel.quantize_weights``)
+    weight_quant: Optional[str] = None   # weight-only projections (``LlamaModel.quantize_weights``): "fp8" (e4m3,
+                                         # per-channel scales) or "mxfp4" (e2m1, one e8m0 scale per 32 elements)
     act_quant: Optional[str] = None      # "fp8" (with weight_quant="fp8"): W8A8 — per-token e4m3 activations and the
                                          # e4m3 GEMM for steps of >= ops.W8A8_MIN_M rows (a token's numerics then
                                          # depend on its step's row count)

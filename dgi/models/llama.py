@@ -142,7 +142,8 @@ class LlamaModel:
         self.norms_folded = False    # fold_norms ran: in_norm / post_norm are ones, qkv / gate_up carry the gains
         self.fold_impl = None        # rows -> run the fused-norm layers? (dgi.runtime.gemm_pad)
         self._ss_buf: Optional[torch.Tensor] = None
-        self.weight_quant: Optional[str] = None     # "fp8": the four projections per layer are ops.Fp8Weight
+        # "fp8" / "mxfp4": the four projections per layer are ops.Fp8Weight / ops.Mxfp4Weight
+        self.weight_quant: Optional[str] = None
         self.act_quant: Optional[str] = None        # "fp8": W8A8 above ops.W8A8_MIN_M rows (quantize_weights)
         self._quant_scratch: Optional[torch.Tensor] = None
         if checkpoint:
@@ -234,31 +235,40 @@ class LlamaModel:
         self.norms_folded = True
 
     def quantize_weights(self, mode: str = "fp8", act_quant: Optional[str] = None) -> "LlamaModel":
-        """Weight-only quantisation of each layer's qkv / o / gate_up / down projection
-        (``ops.quantize_fp8``: e4m3 codes, one fp32 scale per output channel), one layer at a
-        time, dropping the bf16 tensor as it goes.  Norm gains, ``qkv_bias``, ``embed`` and
-        ``lm_head`` keep their dtype.  Steps then run ``_forward_layers_quant``.
+        """Weight-only quantisation of each layer's qkv / o / gate_up / down projection, one layer
+        at a time, dropping the bf16 tensor as it goes: ``"fp8"`` (``ops.quantize_fp8``: e4m3 codes,
+        one fp32 scale per output channel) or ``"mxfp4"`` (``ops.quantize_mxfp4``: e2m1 codes, one
+        e8m0 scale per 32 elements).  Norm gains, ``qkv_bias``, ``embed`` and ``lm_head`` keep their
+        dtype.  Steps then run ``_forward_layers_quant``.
 
-        ``act_quant="fp8"`` (W8A8) marks every quantised projection so that steps of at least
-        ``ops.W8A8_MIN_M`` rows quantise their activations per token and run the e4m3 GEMM
-        (``ops.linear_w8a8``); smaller steps stay W8A16."""
-        if mode != "fp8":
-            raise ValueError(f"quantize_weights: unsupported mode {mode!r} (supported: 'fp8')")
+        ``act_quant="fp8"`` (W8A8, fp8 weights only) marks every quantised projection so that steps
+        of at least ``ops.W8A8_MIN_M`` rows quantise their activations per token and run the e4m3
+        GEMM (``ops.linear_w8a8``); smaller steps stay W8A16."""
+        if mode not in ("fp8", "mxfp4"):
+            raise ValueError(f"quantize_weights: unsupported mode {mode!r} (supported: 'fp8', 'mxfp4')")
         if act_quant not in (None, "fp8"):
             raise ValueError(f"quantize_weights: unsupported act_quant {act_quant!r} (supported: None, 'fp8')")
+        if act_quant and mode != "fp8":
+            raise ValueError(f"quantize_weights: act_quant={act_quant!r} needs mode='fp8' (the e4m3 GEMM reads "
+                             f"e4m3 weights), not {mode!r}")
         if self.weight_quant == mode:
             self._set_act_quant(act_quant)
             return self
+        if self.weight_quant:
+            raise RuntimeError(f"quantize_weights: the model's weights are {self.weight_quant}-quantised already; "
+                               f"quantise a model holding the bf16 weights to {mode!r}")
+        kind, quantise = (ops.Fp8Weight, ops.quantize_fp8) if mode == "fp8" else (ops.Mxfp4Weight, ops.quantize_mxfp4)
         largest = 0
         for L in self.layers:
             for k in QUANT_SLOTS:
                 w = getattr(L, k)
-                if not isinstance(w, ops.Fp8Weight):
-                    setattr(L, k, ops.quantize_fp8(w))
+                if not isinstance(w, kind):
+                    setattr(L, k, quantise(w))
                     del w
-                largest = max(largest, getattr(L, k).q.numel())
+                N, K = getattr(L, k).shape
+                largest = max(largest, N * K)
         # one bf16 buffer the size of the largest projection: the dequantised copy of the steps the
-        # fp8 kernel does not take (allocated here so a graph capture never allocates it)
+        # quantised kernel does not take (allocated here so a graph capture never allocates it)
         if largest and self.device.type == "cuda":
             self._quant_scratch = torch.empty(largest, dtype=torch.bfloat16, device=self.device)
             for L in self.layers:
@@ -272,9 +282,10 @@ class LlamaModel:
         return self
 
     def _set_act_quant(self, act_quant: Optional[str]) -> None:
-        for L in self.layers:
-            for k in QUANT_SLOTS:
-                getattr(L, k).act = act_quant
+        if self.weight_quant == "fp8":      # mxfp4 weights have no activation mode (quantize_weights refuses one)
+            for L in self.layers:
+                for k in QUANT_SLOTS:
+                    getattr(L, k).act = act_quant
         self.act_quant = act_quant
 
     def _check_not_quantised(self, what: str) -> None:
@@ -318,7 +329,7 @@ class LlamaModel:
         for i, L in enumerate(self.layers):
             for k in LlamaLayerWeights.__slots__:
                 t = getattr(L, k)
-                if isinstance(t, ops.Fp8Weight):
+                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight)):
                     yield f"layers.{self.layer_start + i}.{k}.q", t.q
                     yield f"layers.{self.layer_start + i}.{k}.scale", t.scale
                 elif t is not None:
@@ -350,8 +361,8 @@ class LlamaModel:
         n = 0
         for L in self.layers:
             for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias):
-                if isinstance(t, ops.Fp8Weight):
-                    n += t.nbytes()      # 1 byte per element + one fp32 scale per row
+                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight)):
+                    n += t.nbytes()      # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements)
                 elif t is not None:
                     n += t.numel() * t.element_size()
         for t in (self.embed, self.norm):

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from dgi.ops.fp8 import E4M3_MAX, Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
+from dgi.ops.mxfp4 import Mxfp4Weight, quantize_mxfp4  # noqa: F401  (public: ops.Mxfp4Weight, ops.quantize_mxfp4)
 
 _LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_C.so")
 _loaded = False
@@ -649,11 +650,102 @@ def _linear_fp8(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor], out
     return r
 
 
+# MXFP4 weight-only projections (skinny_gemm_mxfp4.hip).  The W4A16 kernel takes every decode-sized
+# step it can launch, as the fp8 kernel does: M <= 32, K % 1024 == 0, N % 16 == 0.  Everything else
+# is dequantised to bf16 (dequant_mxfp4) and runs the bf16 GEMM.  Every mxfp4 value is a bf16 number,
+# so the dequantised weight is exact and both GPU routes multiply the same numbers: a token's result
+# depends on the row count only through the summation order (unlike fp8's dequant route, which
+# rounds each weight once more).
+# launch configs of skinny_gemm_w4: cfg -> (waves per workgroup, column tiles per wave, 256-deep
+# K steps per load group, ring depth at M <= 16); a config needs N % (16 * tiles) == 0 and
+# (K / 256) % (waves * steps) == 0.  Steps of more than 16 rows run rings of at most two groups
+# (one for cfg 8): the X fragment is twice the fp8 kernel's.
+SKINNY_W4_CFGS = {1: (4, 1, 1, 4), 2: (4, 1, 1, 2), 3: (8, 1, 1, 2), 4: (8, 1, 1, 4), 5: (4, 2, 1, 2),
+                  6: (8, 2, 1, 2), 7: (4, 4, 1, 2), 8: (8, 4, 1, 2)}
+SKINNY_W4_CFG = _env_cfg("DGI_SKINNY_W4_CFG", 0, SKINNY_W4_CFGS)    # > 0 forces a launch config (sweeps)
+
+
+def skinny_w4_cfg_ok(cfg: int, N: int, K: int) -> bool:
+    """Whether launch config ``cfg`` of ``skinny_gemm_w4`` divides an [N, K] weight."""
+    nw, nt, u, _d = SKINNY_W4_CFGS[cfg or 2]
+    return K % 1024 == 0 and N % (16 * nt) == 0 and (K // 256) % (nw * u) == 0
+
+
+def _skinny_w4_cfg(M: int, N: int, K: int = 0) -> int:
+    """Launch config per row count and shape (profiles/mxfp4_weights/README.md, weights cold,
+    hipGraph-timed).  The X fragment is read at twice the fp8 kernel's rate per weight byte, so column
+    tiles that share it win earlier than they do for fp8: two tiles per wave (cfg 5) at every row count
+    for 6144 <= N < 16384, four (cfg 7; cfg 8 on two row tiles) for the gate_up widths.  The narrow
+    projections (N = 4096) keep one tile: 8 waves up to two rows, 4 above.  Between one and two
+    workgroups of two tiles per CU (70B qkv: 320 on 256 CUs) one tile up to two rows, four above.
+    The 8-wave configs need K % 2048 == 0; ``K`` unknown picks among the 4-wave ones."""
+    if SKINNY_W4_CFG > 0:
+        return SKINNY_W4_CFG
+    k8 = K > 0 and K % 2048 == 0
+    one = 3 if (M <= 2 and k8) else 0
+    if N < 6144 or N % 64:
+        return one
+    if N >= 16384 or 256 < N // 32 < 512:
+        if N < 16384 and M <= 2:
+            return one
+        return 8 if (M > 16 and k8) else 7
+    return 5
+
+
+def _use_skinny_w4(M: int, N: int, K: int) -> bool:
+    return 0 < M <= min(32, SKINNY_MAX_M) and K % 1024 == 0 and N % 16 == 0
+
+
+def linear_mxfp4_ref(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return torch.nn.functional.linear(x.float(), w.dequant(torch.float32),
+                                      None if bias is None else bias.float()).to(x.dtype)
+
+
+def dequant_mxfp4(w: Mxfp4Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] copy of an mxfp4 weight (exact); ``out``: a flat bf16 buffer of >= N*K elements."""
+    N, K = w.shape
+    if out is None or out.numel() < N * K or out.device != w.device or out.dtype != torch.bfloat16:
+        out = torch.empty(N * K, dtype=torch.bfloat16, device=w.device)
+    out = out.view(-1)[: N * K].view(N, K)
+    if w.q.is_cuda:
+        load_native(required=True)
+        _call("dequant_mxfp4", out, w.q, w.scale)     # K % 32 == 0 by construction, checked by the op
+    else:
+        out.copy_(w.dequant(torch.bfloat16))
+    return out
+
+
+def _linear_mxfp4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor], out: Optional[torch.Tensor]):
+    if x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16:
+        M, K = x.shape
+        N = w.shape[0]
+        if (_use_skinny_w4(M, N, K) and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
+                and (M == 1 or x.stride(0) >= K)):
+            load_native(required=True)
+            direct = (out is not None and out.dtype == torch.bfloat16 and out.shape == (M, N) and out.is_cuda
+                      and out.stride(1) == 1 and (M == 1 or out.stride(0) >= N))
+            r = out if direct else torch.empty(M, N, dtype=x.dtype, device=x.device)
+            _call("skinny_gemm_w4", r, x, w.q, w.scale, bias, _skinny_w4_cfg(M, N, K))
+            if direct:
+                return out
+        else:
+            r = torch.nn.functional.linear(x, dequant_mxfp4(w, w.scratch), bias)
+    else:
+        r = linear_mxfp4_ref(x, w, bias)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
 def linear(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = x @ w.T (+ bias) for a 2-D activation; [N, K] weights as stored (bf16 tensor or ``Fp8Weight``)."""
+    """y = x @ w.T (+ bias) for a 2-D activation; [N, K] weights as stored (bf16 tensor, ``Fp8Weight``
+    or ``Mxfp4Weight``)."""
     if isinstance(w, Fp8Weight):
         return _linear_fp8(x, w, bias, out)
+    if isinstance(w, Mxfp4Weight):
+        return _linear_mxfp4(x, w, bias, out)
     if x.dim() != 2:
         return torch.nn.functional.linear(x, w, bias)
     M, K = x.shape

@@ -400,8 +400,9 @@ def main(argv=None) -> int:
     ap.add_argument("--max-model-len", type=int, default=4096)
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--weight-quant", default=None, choices=["fp8"],
-                    help="weight-only quantisation of the layer projections (default: bf16 weights)")
+    ap.add_argument("--weight-quant", default=None, choices=["fp8", "mxfp4"],
+                    help="weight-only quantisation of the layer projections: fp8 (e4m3) or mxfp4 (OCP e2m1 with e8m0 "
+                         "block scales) (default: bf16 weights)")
     ap.add_argument("--act-quant", default=None, choices=["fp8"],
                     help="with --weight-quant fp8: W8A8, per-token e4m3 activations and the e4m3 GEMM for steps of "
                          "at least DGI_W8A8_MIN_M rows, 2048 unless set (default: bf16 activations at every step size)")

@@ -24,7 +24,7 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=256)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--weight-quant", default=None, choices=["fp8"], help="weight-only quantised projections")
+    ap.add_argument("--weight-quant", default=None, choices=["fp8", "mxfp4"], help="weight-only quantised projections")
     ap.add_argument("--act-quant", default=None, choices=["fp8"],
                     help="with --weight-quant fp8: W8A8 for steps of at least DGI_W8A8_MIN_M rows (default 2048)")
     ap.add_argument("--prefill-tokens", type=int, default=0,

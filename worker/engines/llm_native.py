@@ -15,7 +15,8 @@ Config keys accepted (SURVEY Appendix C mapping): ``model_id``, ``device``,
 ``max_running_requests``/``max_num_seqs``, ``chunked_prefill_size``,
 ``enable_prefix_caching``, ``context_length``/``max_model_len``,
 ``num_blocks``, ``use_graphs``/``enforce_eager``, ``quantization``/``weight_quant``
-(``"fp8"``: weight-only e4m3 projections; anything else is served unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
+(``"fp8"``: weight-only e4m3 projections, ``"mxfp4"``: weight-only OCP MXFP4 projections; anything else is served
+unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
 ``DGI_W8A8_MIN_M`` rows, default 2048; ``quantization: "fp8"`` alone stays W8A16); nested ``sglang``/``vllm``/
 ``native`` dicts are merged in.
 """
@@ -101,15 +102,16 @@ class NativeLLMEngine(LLMBaseEngine):
         quant = c.get("weight_quant", c.get("quantization"))
         if quant is not None and str(quant).lower() in ("", "none"):
             quant = None
-        if quant is not None and str(quant).lower() != "fp8":
-            logger.warning("quantization=%r is not supported by the native engine (supported: 'fp8', weight-only); "
-                           "serving %s unquantised", quant, model_id)
+        if quant is not None and str(quant).lower() not in ("fp8", "mxfp4"):
+            logger.warning("quantization=%r is not supported by the native engine (supported: 'fp8', 'mxfp4', "
+                           "weight-only); serving %s unquantised", quant, model_id)
             quant = None
+        quant = None if quant is None else str(quant).lower()
         # W8A8 is opt-in: quantization "fp8" alone stays weight-only (W8A16)
         actq = c.get("act_quant")
         if actq is not None and str(actq).lower() in ("", "none"):
             actq = None
-        if actq is not None and (str(actq).lower() != "fp8" or quant is None):
+        if actq is not None and (str(actq).lower() != "fp8" or quant != "fp8"):
             logger.warning("act_quant=%r is not supported by the native engine (supported: 'fp8', together with "
                            "quantization 'fp8'); serving %s with bf16 activations", actq, model_id)
             actq = None
@@ -131,7 +133,7 @@ class NativeLLMEngine(LLMBaseEngine):
             enable_prefix_caching=bool(c.get("enable_prefix_caching", True)),
             use_graphs=bool(c.get("use_graphs", not c.get("enforce_eager", False))) and device != "cpu",
             seed=int(c.get("seed", 0)), block_size=int(c.get("block_size", 16)),
-            host_kv_gb=float(c.get("host_kv_gb", 0.0)), weight_quant="fp8" if quant is not None else None,
+            host_kv_gb=float(c.get("host_kv_gb", 0.0)), weight_quant=quant,
             act_quant="fp8" if actq is not None else None,
             kv_dtype="fp8" if kvd is not None else None,
             graph_buckets=tuple(c["graph_batch_buckets"]) if c.get("graph_batch_buckets") else None)

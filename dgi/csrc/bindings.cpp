@@ -17,6 +17,10 @@ int dgi_fused_add_rmsnorm(void* x, void* residual, const void* w, int T, int H, 
 int dgi_rope_cache(void* qkv, int T, int qkv_stride, const int* positions, const float* cos_sin,
                    int nh, int nkv, int hd, int rd, int mode, const int* slot_mapping, void* k_cache,
                    void* v_cache, int block_size, const float* kv_inv_scale, hipStream_t s);
+int dgi_qknorm_rope_cache(void* qkv, int T, int qkv_stride, const int* positions, const float* cos_sin,
+                          const void* q_gain, const void* k_gain, float eps, int nh, int nkv, int hd,
+                          const int* slot_mapping, void* k_cache, void* v_cache, int block_size,
+                          const float* kv_inv_scale, hipStream_t s);
 int dgi_paged_decode(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                      const int* block_tables, int bt_stride, const int* context_lens, void* out,
                      int out_stride, float* part_o, float* part_lse, int* counters, int B, int nh, int nkv,
@@ -168,6 +172,45 @@ void rope_cache(at::Tensor qkv, const at::Tensor& positions, const at::Tensor& c
                           (int)mode, slot_mapping.data_ptr<int>(), k_cache.data_ptr(), v_cache.data_ptr(),
                           (int)k_cache.size(2), inv, cur_stream()),
            "rope_cache");
+}
+
+// rope_cache with a per-head RMSNorm of q and k in front of the rotation (Qwen3): q_gain / k_gain are
+// bf16 [hd]; NeoX pairing over the whole head only, so cos_sin is [max_pos, hd] and hd is 64 or 128
+void qknorm_rope_cache(at::Tensor qkv, const at::Tensor& positions, const at::Tensor& cos_sin,
+                       const at::Tensor& q_gain, const at::Tensor& k_gain, double eps, int64_t nh, int64_t nkv,
+                       int64_t hd, const at::Tensor& slot_mapping, at::Tensor k_cache, at::Tensor v_cache,
+                       const c10::optional<at::Tensor>& kv_inv_scale) {
+  check_bf16(qkv, "qkv"); check_i32(positions, "positions"); check_i32(slot_mapping, "slot_mapping");
+  check_bf16(q_gain, "q_gain"); check_bf16(k_gain, "k_gain");
+  const float* inv = check_kv(k_cache, v_cache, kv_inv_scale, nkv, "qknorm_rope_cache");
+  TORCH_CHECK(nh > 0 && nkv > 0 && (hd == 64 || hd == 128),
+              "qknorm_rope_cache: head_dim must be 64 or 128, got ", hd);
+  TORCH_CHECK(q_gain.dim() == 1 && q_gain.size(0) == hd && q_gain.is_contiguous() && k_gain.dim() == 1 &&
+                  k_gain.size(0) == hd && k_gain.is_contiguous(),
+              "qknorm_rope_cache: q_gain and k_gain must be contiguous [head_dim] tensors");
+  check_dev(cos_sin, "cos_sin");
+  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous() && cos_sin.dim() == 2 &&
+                  cos_sin.size(1) == hd,
+              "qknorm_rope_cache: cos_sin must be a contiguous fp32 [max_pos, head_dim] table (full rotary)");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1 && qkv.size(1) >= (nh + 2 * nkv) * hd);
+  TORCH_CHECK(qkv.device() == q_gain.device() && qkv.device() == k_gain.device() &&
+                  qkv.device() == cos_sin.device() && qkv.device() == k_cache.device() &&
+                  qkv.device() == v_cache.device(),
+              "qknorm_rope_cache: operands on different devices");
+  // 16-byte vector access to the rows and the gains
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && (uintptr_t)qkv.data_ptr() % 16 == 0 &&
+                  (uintptr_t)q_gain.data_ptr() % 16 == 0 && (uintptr_t)k_gain.data_ptr() % 16 == 0,
+              "qknorm_rope_cache: qkv rows and the gains must be 16-byte aligned");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(1) == nkv && k_cache.size(3) == hd &&
+              v_cache.sizes() == k_cache.sizes());
+  const int T = (int)qkv.size(0);
+  TORCH_CHECK(positions.numel() == T && slot_mapping.numel() == T);
+  check_rc(dgi_qknorm_rope_cache(qkv.data_ptr(), T, (int)qkv.stride(0), positions.data_ptr<int>(),
+                                 cos_sin.data_ptr<float>(), q_gain.data_ptr(), k_gain.data_ptr(), (float)eps,
+                                 (int)nh, (int)nkv, (int)hd, slot_mapping.data_ptr<int>(), k_cache.data_ptr(),
+                                 v_cache.data_ptr(), (int)k_cache.size(2), inv, cur_stream()),
+           "qknorm_rope_cache");
 }
 
 // q: [B, >= nh*hd] rows (row stride = q.stride(0)); out: [B, nh*hd]
@@ -784,6 +827,9 @@ TORCH_LIBRARY(dgi, m) {
   m.def("fused_add_rmsnorm(Tensor(a!) x, Tensor(b!) residual, Tensor w, float eps) -> ()");
   m.def("rope_cache(Tensor(a!) qkv, Tensor positions, Tensor cos_sin, int nh, int nkv, int hd, "
         "Tensor slot_mapping, Tensor(b!) k_cache, Tensor(c!) v_cache, int mode=0, Tensor? kv_inv_scale=None) -> ()");
+  m.def("qknorm_rope_cache(Tensor(a!) qkv, Tensor positions, Tensor cos_sin, Tensor q_gain, Tensor k_gain, "
+        "float eps, int nh, int nkv, int hd, Tensor slot_mapping, Tensor(b!) k_cache, Tensor(c!) v_cache, "
+        "Tensor? kv_inv_scale=None) -> ()");
   m.def("paged_decode(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor context_lens, Tensor(b!) part_o, Tensor(c!) part_lse, int nh, int nkv, int max_splits, "
         "int part_size, float scale, Tensor(d!)? counters=None, Tensor? kv_scale=None) -> ()");
@@ -828,6 +874,7 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("rmsnorm", &rmsnorm);
   m.impl("fused_add_rmsnorm", &fused_add_rmsnorm);
   m.impl("rope_cache", &rope_cache);
+  m.impl("qknorm_rope_cache", &qknorm_rope_cache);
   m.impl("paged_decode", &paged_decode);
   m.impl("paged_prefill", &paged_prefill);
   m.impl("silu_mul", &silu_mul);

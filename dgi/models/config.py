@@ -1,4 +1,4 @@
-"""Model configurations (Llama-3 8B/70B, Qwen2.5 7B/0.5B, GLM-4-9B, OPT-125m, tiny test models).
+"""Model configurations (Llama-3 8B/70B, Qwen2.5 7B/0.5B, Qwen3 0.6B/8B/32B, GLM-4-9B, OPT-125m, tiny test models).
 
 Mirrors the fields the reference reads from HF ``AutoConfig``
 (worker/distributed/model_shard.py:273-311 uses hidden_size,
@@ -12,13 +12,14 @@ from __future__ import annotations
 import dataclasses
 import json
 import os
+import re
 from typing import Optional
 
 
 @dataclasses.dataclass
 class ModelConfig:
     name: str
-    arch: str = "llama"  # "llama" | "qwen2" | "opt"
+    arch: str = "llama"  # "llama" | "qwen2" | "qwen3" | "glm" | "opt"
     vocab_size: int = 128256
     hidden_size: int = 4096
     intermediate_size: int = 14336
@@ -34,6 +35,7 @@ class ModelConfig:
     qkv_bias: bool = False          # Qwen2 / GLM-4: biased q/k/v projections
     rotary_dim: Optional[int] = None  # rotated dims per head (GLM-4: head_dim / 2); None = head_dim
     rope_interleaved: bool = False  # GLM-4 / GPT-J pairing (2i, 2i+1) instead of NeoX (i, i+rd/2)
+    qk_norm: bool = False           # Qwen3: RMSNorm over each q and k head (gain [head_dim]) before RoPE
     bos_token_id: int = 128000
     eos_token_id: int = 128001
 
@@ -58,6 +60,8 @@ class ModelConfig:
         per_layer = H * self.qkv_size + self.q_size * H + 2 * H * I + I * H + 2 * H
         if self.qkv_bias:
             per_layer += self.qkv_size
+        if self.qk_norm:
+            per_layer += 2 * self.head_dim
         emb = V * H * (1 if self.tie_embeddings else 2)
         return L * per_layer + emb + H
 
@@ -91,7 +95,15 @@ class ModelConfig:
         eos = d.get("eos_token_id", 2)
         if isinstance(eos, list):
             eos = eos[0]
-        arch = {"qwen2": "qwen2", "glm": "glm"}.get(mt, "llama")
+        arch = {"qwen2": "qwen2", "qwen3": "qwen3", "glm": "glm"}.get(mt, "llama")
+        if mt == "qwen3":
+            # every layer must attend over the whole context: a sliding-window layer served as a
+            # full-attention one would be silently wrong
+            if d.get("use_sliding_window"):
+                raise ValueError(f"{name}: Qwen3 with use_sliding_window is not supported")
+            bad = sorted({t for t in (d.get("layer_types") or []) if t != "full_attention"})
+            if bad:
+                raise ValueError(f"{name}: Qwen3 layer_types {bad} are not supported (full_attention only)")
         hd = d.get("head_dim") or H // nh
         prf = d.get("partial_rotary_factor", rp.get("partial_rotary_factor", 1.0))
         rot = int(hd * prf) if prf and prf < 1.0 else None
@@ -103,7 +115,7 @@ class ModelConfig:
                            max_position=d.get("max_position_embeddings", 8192),
                            tie_embeddings=d.get("tie_word_embeddings", False),
                            qkv_bias=bool(d.get("attention_bias", mt == "qwen2")),
-                           rotary_dim=rot, rope_interleaved=(mt == "glm"),
+                           rotary_dim=rot, rope_interleaved=(mt == "glm"), qk_norm=(mt == "qwen3"),
                            bos_token_id=d.get("bos_token_id", 1), eos_token_id=eos)
 
     @staticmethod
@@ -144,6 +156,27 @@ PRESETS: dict[str, ModelConfig] = {
                              intermediate_size=1536, num_layers=2, num_heads=14, num_kv_heads=2, head_dim=128,
                              rope_theta=1000000.0, rms_eps=1e-6, max_position=4096, tie_embeddings=True,
                              qkv_bias=True, bos_token_id=1, eos_token_id=2),
+    # Qwen3 dense family: the Llama block with no QKV bias, an explicit head_dim of 128 (q_size !=
+    # hidden_size on 0.6B and 32B) and an RMSNorm over each q / k head before RoPE.  Shapes as the
+    # published configs are remembered; they could not be checked offline, and a local config.json
+    # always takes precedence (get_config reads a path before it guesses from a name).
+    "qwen3-8b": ModelConfig(name="qwen3-8b", arch="qwen3", vocab_size=151936, hidden_size=4096,
+                            intermediate_size=12288, num_layers=36, num_heads=32, num_kv_heads=8, head_dim=128,
+                            rope_theta=1000000.0, rms_eps=1e-6, max_position=40960, qk_norm=True,
+                            bos_token_id=151643, eos_token_id=151645),
+    "qwen3-32b": ModelConfig(name="qwen3-32b", arch="qwen3", vocab_size=151936, hidden_size=5120,
+                             intermediate_size=25600, num_layers=64, num_heads=64, num_kv_heads=8, head_dim=128,
+                             rope_theta=1000000.0, rms_eps=1e-6, max_position=40960, qk_norm=True,
+                             bos_token_id=151643, eos_token_id=151645),
+    "qwen3-0.6b": ModelConfig(name="qwen3-0.6b", arch="qwen3", vocab_size=151936, hidden_size=1024,
+                              intermediate_size=3072, num_layers=28, num_heads=16, num_kv_heads=8, head_dim=128,
+                              rope_theta=1000000.0, rms_eps=1e-6, max_position=40960, tie_embeddings=True,
+                              qk_norm=True, bos_token_id=151643, eos_token_id=151645),
+    # tiny Qwen3 for tests: q_size = 2 * hidden_size on purpose, 2 KV heads (TP=2 has one per rank)
+    "qwen3-tiny": ModelConfig(name="qwen3-tiny", arch="qwen3", vocab_size=1024, hidden_size=1024,
+                              intermediate_size=2048, num_layers=2, num_heads=16, num_kv_heads=2, head_dim=128,
+                              rope_theta=1000000.0, rms_eps=1e-6, max_position=4096, tie_embeddings=True,
+                              qk_norm=True, bos_token_id=1, eos_token_id=2),
     # GLM-4-9B (HF "glm"): Llama block + biased QKV, GQA 16:1, half-dim interleaved RoPE
     "glm-4-9b": ModelConfig(name="glm-4-9b", arch="glm", vocab_size=151552, hidden_size=4096,
                             intermediate_size=13696, num_layers=40, num_heads=32, num_kv_heads=2, head_dim=128,
@@ -169,6 +202,9 @@ ALIASES = {
     "Qwen/Qwen2.5-7B": "qwen2.5-7b",
     "Qwen/Qwen2-7B-Instruct": "qwen2.5-7b",
     "Qwen/Qwen2.5-0.5B-Instruct": "qwen2.5-0.5b",
+    "Qwen/Qwen3-8B": "qwen3-8b",
+    "Qwen/Qwen3-32B": "qwen3-32b",
+    "Qwen/Qwen3-0.6B": "qwen3-0.6b",
     "THUDM/glm-4-9b-chat-hf": "glm-4-9b",
     "THUDM/glm-4-9b-chat": "glm-4-9b",
     "THUDM/glm-4-9b-hf": "glm-4-9b",
@@ -190,6 +226,16 @@ def get_config(name_or_path: str) -> ModelConfig:
     lk = key.lower()
     if "glm-4" in lk or "glm4" in lk:
         return dataclasses.replace(PRESETS["glm-4-9b"], name=name_or_path)
+    if "qwen3" in lk:
+        # the size comes from the name; a size without a preset (the MoE models, "-A3B", included)
+        # is an error, never a guess
+        tail = lk.split("qwen3", 1)[1]
+        if not re.search(r"-a\d+(\.\d+)?b", tail):
+            for size in ("0.6b", "32b", "8b"):
+                if re.search(rf"(?<![\d.]){re.escape(size)}(?![\d])", tail):
+                    return dataclasses.replace(PRESETS["qwen3-" + size], name=name_or_path)
+        raise KeyError(f"unknown Qwen3 model {name_or_path!r}: presets exist for "
+                       f"{sorted(k for k in PRESETS if k.startswith('qwen3-'))}; pass a local config.json")
     if "qwen" in lk:
         return dataclasses.replace(PRESETS["qwen2.5-0.5b" if "0.5b" in lk else "qwen2.5-7b"], name=name_or_path)
     if "70b" in lk:

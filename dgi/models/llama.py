@@ -10,7 +10,8 @@ worker/distributed/model_shard.py:28-246).  Per layer the step runs
 with fused QKV and gate|up weights so each layer issues 4 GEMMs.  Qwen2's biased
 q/k/v projections ride in the QKV GEMM's bias epilogue (hipBLASLt), so the
 family adds no kernel; GLM-4 adds biased QKV and half-dim interleaved RoPE
-(``rope_cache`` mode 1 over the first ``rotary_dim`` dims).  A model
+(``rope_cache`` mode 1 over the first ``rotary_dim`` dims); Qwen3 drops the bias and
+normalises every q and k head before RoPE, inside the writer (``qknorm_rope_cache``).  A model
 object may hold any contiguous layer range (pipeline stage): stage 0 owns the
 embedding, the last stage the final norm and LM head, exactly like the
 reference's ``ModelShard`` (model_shard.py:28-59).  Between stages a single
@@ -82,12 +83,14 @@ def _ss_cols(hidden: int) -> int:
 
 
 class LlamaLayerWeights:
-    __slots__ = ("in_norm", "qkv", "o", "post_norm", "gate_up", "down", "qkv_bias")
+    __slots__ = ("in_norm", "qkv", "o", "post_norm", "gate_up", "down", "qkv_bias", "q_norm", "k_norm")
 
-    def __init__(self, in_norm, qkv, o, post_norm, gate_up, down, qkv_bias=None):
+    def __init__(self, in_norm, qkv, o, post_norm, gate_up, down, qkv_bias=None, q_norm=None, k_norm=None):
         self.in_norm, self.qkv, self.o = in_norm, qkv, o
         self.post_norm, self.gate_up, self.down = post_norm, gate_up, down
         self.qkv_bias = qkv_bias   # [qkv_size] for Qwen2, else None (fused into the QKV GEMM epilogue)
+        # [head_dim] gains of the per-head q / k RMSNorm for Qwen3, else None (ops.qknorm_rope_cache)
+        self.q_norm, self.k_norm = q_norm, k_norm
 
 
 QUANT_SLOTS = ("qkv", "o", "gate_up", "down")    # the projections quantize_weights replaces
@@ -158,6 +161,11 @@ class LlamaModel:
         self.cos_sin = ops.rope_cos_sin(cfg.rope_dim, cfg.max_position, cfg.rope_theta, cfg.rope_scaling,
                                         device=self.device)
         self.rope_mode = 1 if cfg.rope_interleaved else 0
+        if cfg.qk_norm and self.device.type == "cuda" and \
+                not ops.qknorm_rope_cache_ok(cfg.head_dim, cfg.rope_dim, self.rope_mode):
+            raise ValueError(f"{cfg.name}: q/k norm on the GPU needs NeoX rotary over the whole head and head_dim "
+                             f"64 or 128 (the qknorm_rope_cache kernel); got head_dim {cfg.head_dim}, rotary_dim "
+                             f"{cfg.rope_dim}, {'interleaved' if self.rope_mode else 'NeoX'} pairing")
 
     # ------------------------------------------------------------------ weights
     def _init_empty(self):
@@ -168,7 +176,9 @@ class LlamaModel:
                 torch.ones(H, device=dev, dtype=dt), torch.empty(c.qkv_size, H, device=dev, dtype=dt),
                 torch.empty(H, c.q_size, device=dev, dtype=dt), torch.ones(H, device=dev, dtype=dt),
                 torch.empty(2 * I, H, device=dev, dtype=dt), torch.empty(H, I, device=dev, dtype=dt),
-                torch.zeros(c.qkv_size, device=dev, dtype=dt) if c.qkv_bias else None))
+                torch.zeros(c.qkv_size, device=dev, dtype=dt) if c.qkv_bias else None,
+                torch.ones(c.head_dim, device=dev, dtype=dt) if c.qk_norm else None,
+                torch.ones(c.head_dim, device=dev, dtype=dt) if c.qk_norm else None))
         if self.has_embed:
             self.embed = torch.empty(c.vocab_size, H, device=dev, dtype=dt)
         if self.has_head:
@@ -195,7 +205,12 @@ class LlamaModel:
             gu = _rand((2 * I, H), gen, dev, dt, std)
             down = _rand((H, I), gen, dev, dt, std / math.sqrt(2 * c.num_layers))
             bias = _rand((c.qkv_size,), gen, dev, dt, std) if c.qkv_bias else None
-            self.layers.append(LlamaLayerWeights(ln1.to(dt), qkv, o, ln2.to(dt), gu, down, bias))
+            # drawn after every other tensor of the layer: models without the norm keep their weights
+            qn = kn = None
+            if c.qk_norm:
+                qn = (1.0 + 0.1 * _rand((c.head_dim,), gen, dev, torch.float32, 1.0)).to(dt)
+                kn = (1.0 + 0.1 * _rand((c.head_dim,), gen, dev, torch.float32, 1.0)).to(dt)
+            self.layers.append(LlamaLayerWeights(ln1.to(dt), qkv, o, ln2.to(dt), gu, down, bias, qn, kn))
         if self.has_embed or (self.has_head and c.tie_embeddings):
             gen.manual_seed(seed * 1000003 + 17)
             emb = _rand((c.vocab_size, H), gen, dev, dt, 1.0)
@@ -238,8 +253,8 @@ class LlamaModel:
         """Weight-only quantisation of each layer's qkv / o / gate_up / down projection, one layer
         at a time, dropping the bf16 tensor as it goes: ``"fp8"`` (``ops.quantize_fp8``: e4m3 codes,
         one fp32 scale per output channel) or ``"mxfp4"`` (``ops.quantize_mxfp4``: e2m1 codes, one
-        e8m0 scale per 32 elements).  Norm gains, ``qkv_bias``, ``embed`` and ``lm_head`` keep their
-        dtype.  Steps then run ``_forward_layers_quant``.
+        e8m0 scale per 32 elements).  Norm gains (``q_norm`` / ``k_norm`` included), ``qkv_bias``,
+        ``embed`` and ``lm_head`` keep their dtype.  Steps then run ``_forward_layers_quant``.
 
         ``act_quant="fp8"`` (W8A8, fp8 weights only) marks every quantised projection so that steps
         of at least ``ops.W8A8_MIN_M`` rows quantise their activations per token and run the e4m3
@@ -307,6 +322,9 @@ class LlamaModel:
             if L.qkv_bias is not None:
                 L.qkv_bias.copy_(torch.cat([sd[p + "self_attn.q_proj.bias"], sd[p + "self_attn.k_proj.bias"],
                                             sd[p + "self_attn.v_proj.bias"]], 0))
+            if L.q_norm is not None:       # Qwen3: a state dict without the two gains is a KeyError
+                L.q_norm.copy_(sd[p + "self_attn.q_norm.weight"])
+                L.k_norm.copy_(sd[p + "self_attn.k_norm.weight"])
             L.o.copy_(sd[p + "self_attn.o_proj.weight"])
             if p + "mlp.gate_up_proj.weight" in sd:     # GLM: fused [gate; up]
                 L.gate_up.copy_(sd[p + "mlp.gate_up_proj.weight"])
@@ -360,7 +378,7 @@ class LlamaModel:
     def weight_bytes(self) -> int:
         n = 0
         for L in self.layers:
-            for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias):
+            for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias, L.q_norm, L.k_norm):
                 if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight)):
                     n += t.nbytes()      # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements)
                 elif t is not None:
@@ -395,7 +413,14 @@ class LlamaModel:
             if self.kv_scale is None or self.kv_scale.shape[0] != self.kv_cache.shape[0]:
                 raise RuntimeError("fp8 KV cache without its scales: bind the pool with LlamaModel.bind_kv")
             ksc, kinv = self.kv_scale[li], self.kv_inv_scale[li]
-        if rope:       # else the qkv GEMM epilogue already rotated q/k and wrote the cache
+        if c.qk_norm:
+            if not rope:
+                raise RuntimeError("q/k norm: the RoPE + KV-write GEMM epilogues rotate before the norm")
+            L = self.layers[li]
+            ops.qknorm_rope_cache(qkv, meta.positions, self.cos_sin, L.q_norm, L.k_norm, c.rms_eps, c.num_heads,
+                                  c.num_kv_heads, c.head_dim, meta.slot_mapping, kc, vc, self.rope_mode,
+                                  kv_inv_scale=kinv)
+        elif rope:     # else the qkv GEMM epilogue already rotated q/k and wrote the cache
             ops.rope_cache(qkv, meta.positions, self.cos_sin, c.num_heads, c.num_kv_heads, c.head_dim,
                            meta.slot_mapping, kc, vc, self.rope_mode, kv_inv_scale=kinv)
         T = qkv.shape[0]
@@ -502,7 +527,9 @@ class LlamaModel:
         eps = c.rms_eps
         T = h.shape[0]
         # the RoPE + KV-write epilogue writes bf16 pages only: an fp8 pool takes the plain epilogue + rope_cache
-        rope_epi = self.rope_mode == 0 and c.head_dim == 128 and self.cos_sin.shape[1] == 128 and not self.kv_fp8
+        # (and rotates the raw projection: a model with q/k norms takes the plain epilogue + qknorm_rope_cache)
+        rope_epi = (self.rope_mode == 0 and c.head_dim == 128 and self.cos_sin.shape[1] == 128 and not self.kv_fp8
+                    and not c.qk_norm)
         for i, L in enumerate(self.layers):
             kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
             if fuse_qkv:
@@ -594,7 +621,7 @@ class LlamaModel:
         n = len(self.layers)
         rope_epi = (NORM_FOLD_ROPE and (R.is_cuda or NORM_FOLD == "force-cpu") and self.rope_mode == 0 and c.head_dim == 128
                     and self.cos_sin.shape[1] == 128 and (c.num_heads * 128) % 256 == 0
-                    and (c.num_kv_heads * 128) % 256 == 0 and not self.kv_fp8)
+                    and (c.num_kv_heads * 128) % 256 == 0 and not self.kv_fp8 and not c.qk_norm)
         for i, L in enumerate(self.layers):
             if rope_epi:
                 qkv = ops.mfma_gemm_norm_rope(R, L.qkv, ss, eps, meta.positions, self.cos_sin, meta.slot_mapping,

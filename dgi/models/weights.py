@@ -160,6 +160,13 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
             _put(L.qkv_bias[ql:ql + kl], rd.read(a + "k_proj.bias", rows=kv_rows))
             _put(L.qkv_bias[ql + kl:], rd.read(a + "v_proj.bias", rows=kv_rows))
             n += 3
+        if L.q_norm is not None:
+            # Qwen3's per-head gains [head_dim]: not sharded, every TP rank reads them whole
+            for slot, name in ((L.q_norm, a + "q_norm.weight"), (L.k_norm, a + "k_norm.weight")):
+                if name not in rd:
+                    raise KeyError(f"{path}: {model.cfg.arch} checkpoint without {name}")
+                _put(slot, rd.read(name))
+            n += 2
         _put(L.o, rd.read(a + "o_proj.weight", cols=q_rows) if tp > 1 else rd.read(a + "o_proj.weight"))
         m = p + "mlp."
         if m + "gate_up_proj.weight" in rd:        # GLM-4: fused [gate; up]

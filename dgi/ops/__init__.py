@@ -251,6 +251,45 @@ def rope_cache(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_ca
         rope_cache_ref(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode, kv_inv_scale)
 
 
+def qknorm_rope_cache_ref(qkv, positions, cos_sin, q_gain, k_gain, eps, nh, nkv, hd, slot_mapping, k_cache, v_cache,
+                          mode: int = 0, kv_inv_scale=None) -> None:
+    """The definition of ``qknorm_rope_cache``: ``rmsnorm_ref`` over every q head (``q_gain``) and
+    every k head (``k_gain``), written back into ``qkv``, then ``rope_cache_ref``."""
+    T = qkv.shape[0]
+    if T == 0:
+        return
+    q = qkv[:, : nh * hd].view(T, nh, hd)
+    k = qkv[:, nh * hd:(nh + nkv) * hd].view(T, nkv, hd)
+    qkv[:, : nh * hd] = rmsnorm_ref(q, q_gain, eps).reshape(T, nh * hd)
+    qkv[:, nh * hd:(nh + nkv) * hd] = rmsnorm_ref(k, k_gain, eps).reshape(T, nkv * hd)
+    rope_cache_ref(qkv, positions, cos_sin, nh, nkv, hd, slot_mapping, k_cache, v_cache, mode, kv_inv_scale)
+
+
+def qknorm_rope_cache(qkv, positions, cos_sin, q_gain, k_gain, eps, nh, nkv, hd, slot_mapping, k_cache, v_cache,
+                      mode: int = 0, kv_inv_scale=None) -> None:
+    """``rope_cache`` with a per-head RMSNorm of q and k in front of the rotation (Qwen3):
+    every q head is normalised over its ``hd`` dims with the bf16 gain ``q_gain`` ``[hd]``, every
+    k head with ``k_gain``, each rounded to the activation dtype as ``rmsnorm`` does, then rotated
+    and written as ``rope_cache`` does; v is copied untouched.  The HIP kernel takes NeoX pairing
+    (``mode`` 0) over the whole head (``cos_sin`` ``[max_pos, hd]``) with ``hd`` 64 or 128 and
+    refuses anything else; the CPU reference is a composition and takes every geometry."""
+    if _native(qkv):
+        if mode != 0:
+            raise ValueError("qknorm_rope_cache: the HIP kernel rotates NeoX pairs only (mode 0), "
+                             f"got mode {mode}")
+        inv = _kv_scale_for(k_cache, kv_inv_scale, "qknorm_rope_cache")
+        _call("qknorm_rope_cache", qkv, positions, cos_sin, q_gain, k_gain, eps, nh, nkv, hd, slot_mapping,
+              k_cache, v_cache, inv)
+    else:
+        qknorm_rope_cache_ref(qkv, positions, cos_sin, q_gain, k_gain, eps, nh, nkv, hd, slot_mapping,
+                              k_cache, v_cache, mode, kv_inv_scale)
+
+
+def qknorm_rope_cache_ok(hd: int, rd: int, mode: int) -> bool:
+    """Whether the HIP ``qknorm_rope_cache`` kernel takes this geometry."""
+    return hd in (64, 128) and rd == hd and mode == 0
+
+
 # ----------------------------------------------------------------------------
 # Attention
 # ----------------------------------------------------------------------------

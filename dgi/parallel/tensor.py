@@ -86,7 +86,12 @@ class TPLlamaModel(LlamaModel):
             gu_l = torch.cat([gu[r * Il:(r + 1) * Il], gu[I + r * Il:I + (r + 1) * Il]]).contiguous()
             down_l = down[:, r * Il:(r + 1) * Il].contiguous()
             del qkv, o, gu, down
-            self.layers.append(LlamaLayerWeights(ln1.to(dt), qkv_l, o_l, ln2.to(dt), gu_l, down_l, bias_l))
+            # per-head gains (Qwen3): every rank holds them whole; drawn last, as LlamaModel does
+            qn = kn = None
+            if full.qk_norm:
+                qn = (1.0 + 0.1 * _rand((hd,), gen, dev, torch.float32, 1.0)).to(dt)
+                kn = (1.0 + 0.1 * _rand((hd,), gen, dev, torch.float32, 1.0)).to(dt)
+            self.layers.append(LlamaLayerWeights(ln1.to(dt), qkv_l, o_l, ln2.to(dt), gu_l, down_l, bias_l, qn, kn))
         gen.manual_seed(seed * 1000003 + 17)
         emb = _rand((full.vocab_size, H), gen, dev, dt, 1.0)
         self.embed = emb

@@ -81,6 +81,15 @@ int dgi_tree_mask(const int* parent, int B, int N, unsigned long long* anc, int*
 int dgi_tree_verify(const int* parent, const long long* draft, const long long* target, int B,
                     int N, const unsigned long long* anc, const int* depth, int* accept_len,
                     int* path, long long* out_tokens, int max_path, hipStream_t s);
+int dgi_moe_route(const void* logits, int is_bf16, int ld, int T, int E, int k, int norm, int* ids, float* weights,
+                  hipStream_t s);
+int dgi_moe_capacity(int n, int E, int BM);
+int dgi_moe_align(const int* ids, int n, int E, int BM, int P, int* counts, int* offsets, int* sorted_slot,
+                  int* block_expert, int* inv, hipStream_t s);
+int dgi_moe_gemm(const void* x, int ldx, const void* w, const int* sorted_slot, const int* block_expert, void* y,
+                 int ldy, int P, int N, int K, int kdiv, int nslots, int E, int BM, int epi, hipStream_t s);
+int dgi_moe_combine(const void* y, int ldy, const int* inv, const float* weights, void* out, int T, int k, int H,
+                    int P, hipStream_t s);
 }
 
 namespace {
@@ -286,6 +295,89 @@ void silu_mul(at::Tensor out, const at::Tensor& gu) {
   TORCH_CHECK(gu.size(-1) == 2 * I && gu.numel() == 2 * out.numel());
   check_rc(dgi_silu_mul(gu.data_ptr(), out.data_ptr(), (int)(out.numel() / I), I, cur_stream()),
            "silu_mul");
+}
+
+// ---- mixture of experts (moe.hip).  Every workspace is an argument: nothing is allocated here.
+// logits [T, E] bf16 / fp32 -> ids [T, k] int32 (descending logit, ties to the lower expert), weights [T, k] fp32
+void moe_route(at::Tensor ids, at::Tensor weights, const at::Tensor& logits, int64_t k, bool norm) {
+  check_dev(logits, "logits"); check_i32(ids, "ids"); check_dev(weights, "weights");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
+              "moe_route: logits must be bfloat16 or float32");
+  TORCH_CHECK(logits.dim() == 2 && (logits.size(1) <= 1 || logits.stride(1) == 1) &&
+                  (logits.size(0) <= 1 || logits.stride(0) >= logits.size(1)),
+              "moe_route: logits must be 2-D with dense rows");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(E >= 1 && E <= 256 && k >= 1 && k <= 16 && k <= E, "moe_route: needs E <= 256 and 1 <= k <= min(E, 16), got E ",
+              E, ", k ", k);
+  TORCH_CHECK(weights.scalar_type() == at::kFloat && weights.is_contiguous() && ids.numel() == T * k &&
+                  weights.numel() == T * k, "moe_route: ids int32 [T, k], weights fp32 [T, k]");
+  TORCH_CHECK(ids.device() == logits.device() && weights.device() == logits.device(), "moe_route: one device");
+  check_rc(dgi_moe_route(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, (int)std::max<int64_t>(logits.stride(0), E),
+                         (int)T, (int)E, (int)k, norm ? 1 : 0, ids.data_ptr<int>(), weights.data_ptr<float>(),
+                         cur_stream()),
+           "moe_route");
+}
+
+// ids [n] int32 -> counts [E], offsets [E + 1], sorted_slot [P], block_expert [P / BM], inv [n]
+void moe_align(at::Tensor counts, at::Tensor offsets, at::Tensor sorted_slot, at::Tensor block_expert, at::Tensor inv,
+               const at::Tensor& ids, int64_t E, int64_t BM) {
+  check_i32(ids, "ids"); check_i32(counts, "counts"); check_i32(offsets, "offsets");
+  check_i32(sorted_slot, "sorted_slot"); check_i32(block_expert, "block_expert"); check_i32(inv, "inv");
+  const int64_t n = ids.numel();
+  TORCH_CHECK(n >= 1 && n < (1ll << 30), "moe_align: slot count out of range");
+  TORCH_CHECK(E >= 1 && E <= 256 && (BM == 16 || BM == 32), "moe_align: needs E <= 256 and BM 16 or 32");
+  const int64_t P = dgi_moe_capacity((int)n, (int)E, (int)BM);
+  TORCH_CHECK(counts.numel() == E && offsets.numel() == E + 1 && sorted_slot.numel() == P &&
+                  block_expert.numel() == P / BM && inv.numel() == n, "moe_align: workspace sizes");
+  for (const at::Tensor* t : {&counts, &offsets, &sorted_slot, &block_expert, &inv})
+    TORCH_CHECK(t->device() == ids.device(), "moe_align: one device");
+  check_rc(dgi_moe_align(ids.data_ptr<int>(), (int)n, (int)E, (int)BM, (int)P, counts.data_ptr<int>(),
+                         offsets.data_ptr<int>(), sorted_slot.data_ptr<int>(), block_expert.data_ptr<int>(),
+                         inv.data_ptr<int>(), cur_stream()),
+           "moe_align");
+}
+
+// out [P, N]; epi 0: x [P, K] in sorted order, w [E, N, K]; epi 1 (SwiGLU): x [T, K] gathered through
+// sorted_slot / k, w [E, 2N, K] = [gate; up].  nslots = T * k bounds every slot the kernel follows.
+void moe_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, const at::Tensor& sorted_slot,
+              const at::Tensor& block_expert, int64_t k, int64_t nslots, int64_t epi, int64_t BM) {
+  check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
+  check_i32(sorted_slot, "sorted_slot"); check_i32(block_expert, "block_expert");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 3 && out.dim() == 2, "moe_gemm: x and out 2-D, w 3-D");
+  TORCH_CHECK(x.stride(1) == 1 && out.is_contiguous() && w.is_contiguous(), "moe_gemm: row-major operands");
+  TORCH_CHECK(epi == 0 || epi == 1, "moe_gemm: epi 0 (plain) or 1 (SwiGLU)");
+  TORCH_CHECK(BM == 16 || BM == 32, "moe_gemm: BM 16 or 32");
+  const int64_t P = sorted_slot.numel(), K = x.size(1), E = w.size(0), N = out.size(1);
+  TORCH_CHECK(P % BM == 0 && block_expert.numel() == P / BM && out.size(0) == P, "moe_gemm: layout sizes");
+  TORCH_CHECK(w.size(2) == K && w.size(1) == (epi ? 2 * N : N), "moe_gemm: shape mismatch");
+  TORCH_CHECK(K % 256 == 0 && N % 16 == 0 && E <= 256 && x.stride(0) % 8 == 0, "moe_gemm: K%256, N%16, E<=256");
+  TORCH_CHECK(k >= 1 && nslots >= 1 && nslots < (1ll << 30), "moe_gemm: k and nslots");
+  // every row the kernel can follow lies inside x
+  TORCH_CHECK(epi ? (nslots - 1) / k < x.size(0) : x.size(0) == P,
+              "moe_gemm: x needs nslots / k rows (SwiGLU) or the sorted layout's P rows (plain)");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)w.data_ptr() % 16 == 0, "moe_gemm: 16-byte alignment");
+  for (const at::Tensor* t : {&x, &w, &sorted_slot, &block_expert})
+    TORCH_CHECK(t->device() == out.device(), "moe_gemm: one device");
+  check_rc(dgi_moe_gemm(x.data_ptr(), (int)x.stride(0), w.data_ptr(), sorted_slot.data_ptr<int>(),
+                        block_expert.data_ptr<int>(), out.data_ptr(), (int)out.stride(0), (int)P, (int)N, (int)K,
+                        epi ? (int)k : 0, (int)nslots, (int)E, (int)BM, (int)epi, cur_stream()),
+           "moe_gemm");
+}
+
+// out [T, H] = bf16(sum_j weights[t, j] * y[inv[t*k + j]]), y [P, H]
+void moe_combine(at::Tensor out, const at::Tensor& y, const at::Tensor& inv, const at::Tensor& weights) {
+  check_bf16(out, "out"); check_bf16(y, "y"); check_i32(inv, "inv"); check_dev(weights, "weights");
+  TORCH_CHECK(out.dim() == 2 && y.dim() == 2 && weights.dim() == 2 && out.is_contiguous() && y.is_contiguous() &&
+                  weights.is_contiguous() && weights.scalar_type() == at::kFloat, "moe_combine: contiguous 2-D operands");
+  const int64_t T = out.size(0), H = out.size(1), k = weights.size(1);
+  TORCH_CHECK(weights.size(0) == T && inv.numel() == T * k && y.size(1) == H && H % 8 == 0 && k >= 1 && k <= 16,
+              "moe_combine: shape mismatch");
+  TORCH_CHECK((uintptr_t)y.data_ptr() % 16 == 0 && (uintptr_t)out.data_ptr() % 16 == 0, "moe_combine: 16-byte alignment");
+  for (const at::Tensor* t : {&y, &inv, &weights})
+    TORCH_CHECK(t->device() == out.device(), "moe_combine: one device");
+  check_rc(dgi_moe_combine(y.data_ptr(), (int)y.stride(0), inv.data_ptr<int>(), weights.data_ptr<float>(),
+                           out.data_ptr(), (int)T, (int)k, (int)H, (int)y.size(0), cur_stream()),
+           "moe_combine");
 }
 
 void skinny_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w,
@@ -837,6 +929,12 @@ TORCH_LIBRARY(dgi, m) {
         "Tensor cu_seqlens_q, Tensor context_lens, Tensor tiles, int nh, int nkv, float scale, "
         "Tensor? tree_mask, int tree_n, int tile_rows=128, Tensor? kv_scale=None) -> ()");
   m.def("silu_mul(Tensor(a!) out, Tensor gu) -> ()");
+  m.def("moe_route(Tensor(a!) ids, Tensor(b!) weights, Tensor logits, int k, bool norm) -> ()");
+  m.def("moe_align(Tensor(a!) counts, Tensor(b!) offsets, Tensor(c!) sorted_slot, Tensor(d!) block_expert, "
+        "Tensor(e!) inv, Tensor ids, int E, int BM) -> ()");
+  m.def("moe_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor sorted_slot, Tensor block_expert, int k, int nslots, "
+        "int epi, int BM) -> ()");
+  m.def("moe_combine(Tensor(a!) out, Tensor y, Tensor inv, Tensor weights) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
   m.def("skinny_gemm_w8(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");
   m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
@@ -878,6 +976,10 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("paged_decode", &paged_decode);
   m.impl("paged_prefill", &paged_prefill);
   m.impl("silu_mul", &silu_mul);
+  m.impl("moe_route", &moe_route);
+  m.impl("moe_align", &moe_align);
+  m.impl("moe_gemm", &moe_gemm);
+  m.impl("moe_combine", &moe_combine);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("skinny_gemm_w8", &skinny_gemm_w8);
   m.impl("dequant_fp8", &dequant_fp8);

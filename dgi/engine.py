@@ -161,6 +161,9 @@ class LLMEngine:
             self.checkpoint = resolve_checkpoint(cfg.model, cfg.model_path)
         self.model_cfg = model_cfg or get_config(self.checkpoint or cfg.model)
         self.model_cfg.max_position = max(self.model_cfg.max_position, cfg.max_model_len)
+        if cfg.weight_quant and self.model_cfg.is_moe:
+            raise ValueError(f"EngineConfig.weight_quant={cfg.weight_quant!r}: {self.model_cfg.name} is a MoE model; "
+                             f"quantised experts are not supported")
         t0 = time.perf_counter()
         self.model = model or LlamaModel(self.model_cfg, self.device, cfg.dtype, cfg.layer_start, cfg.layer_end,
                                          seed=cfg.seed, checkpoint=self.checkpoint)
@@ -232,7 +235,9 @@ class LLMEngine:
                       "finished": 0, "step_time": 0.0}
         # MLP row padding measured on this GPU (hipBLASLt kernel-selection cliffs, dgi.runtime.gemm_pad)
         self.mlp_pad_table = None
-        quantised = getattr(self.model, "weight_quant", None) is not None   # no bf16 weights to time or fold
+        # no bf16 weights to time or fold; a MoE model has no dense gate_up / down to route (it always
+        # runs the unfused layers)
+        quantised = getattr(self.model, "weight_quant", None) is not None or self.model_cfg.is_moe
         if self.device.type == "cuda" and getattr(self.model, "mlp_pad", None) is None and not quantised:
             from dgi.runtime.gemm_pad import build_for_model
             t1 = time.perf_counter()

@@ -1,4 +1,4 @@
-"""Model configurations (Llama-3 8B/70B, Qwen2.5 7B/0.5B, Qwen3 0.6B/8B/32B, GLM-4-9B, OPT-125m, tiny test models).
+"""Model configurations (Llama-3 8B/70B, Qwen2.5 7B/0.5B, Qwen3 0.6B/8B/32B, Qwen3-30B-A3B (MoE), GLM-4-9B, OPT-125m, tiny test models).
 
 Mirrors the fields the reference reads from HF ``AutoConfig``
 (worker/distributed/model_shard.py:273-311 uses hidden_size,
@@ -19,7 +19,7 @@ from typing import Optional
 @dataclasses.dataclass
 class ModelConfig:
     name: str
-    arch: str = "llama"  # "llama" | "qwen2" | "qwen3" | "glm" | "opt"
+    arch: str = "llama"  # "llama" | "qwen2" | "qwen3" | "qwen3_moe" | "glm" | "opt"
     vocab_size: int = 128256
     hidden_size: int = 4096
     intermediate_size: int = 14336
@@ -38,6 +38,16 @@ class ModelConfig:
     qk_norm: bool = False           # Qwen3: RMSNorm over each q and k head (gain [head_dim]) before RoPE
     bos_token_id: int = 128000
     eos_token_id: int = 128001
+    # Qwen3-MoE: every layer's MLP is num_experts_per_tok of num_experts SwiGLU experts of width
+    # moe_intermediate_size (no shared expert); num_experts == 0 is a dense model
+    num_experts: int = 0
+    num_experts_per_tok: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = False      # renormalise the k chosen probabilities to sum to one
+
+    @property
+    def is_moe(self) -> bool:
+        return self.num_experts > 0
 
     @property
     def rope_dim(self) -> int:
@@ -57,7 +67,10 @@ class ModelConfig:
 
     def param_count(self) -> int:
         H, I, V, L = self.hidden_size, self.intermediate_size, self.vocab_size, self.num_layers
-        per_layer = H * self.qkv_size + self.q_size * H + 2 * H * I + I * H + 2 * H
+        mlp = 2 * H * I + I * H
+        if self.is_moe:     # the router and the experts' gate, up and down
+            mlp = self.num_experts * (H + 3 * H * self.moe_intermediate_size)
+        per_layer = H * self.qkv_size + self.q_size * H + mlp + 2 * H
         if self.qkv_bias:
             per_layer += self.qkv_size
         if self.qk_norm:
@@ -95,8 +108,25 @@ class ModelConfig:
         eos = d.get("eos_token_id", 2)
         if isinstance(eos, list):
             eos = eos[0]
-        arch = {"qwen2": "qwen2", "qwen3": "qwen3", "glm": "glm"}.get(mt, "llama")
-        if mt == "qwen3":
+        arch = {"qwen2": "qwen2", "qwen3": "qwen3", "qwen3_moe": "qwen3_moe", "glm": "glm"}.get(mt, "llama")
+        moe = {}
+        if mt == "qwen3_moe":
+            # the published files say num_experts; transformers 5 save_pretrained writes num_local_experts
+            ne = d.get("num_experts") or d.get("num_local_experts")
+            if not ne:
+                raise ValueError(f"{name}: qwen3_moe config without num_experts / num_local_experts")
+            # every layer must be sparse: a dense layer served through the experts (or the reverse)
+            # would be silently wrong
+            if d.get("decoder_sparse_step", 1) != 1:
+                raise ValueError(f"{name}: Qwen3-MoE with decoder_sparse_step="
+                                 f"{d.get('decoder_sparse_step')} is not supported (every layer must be sparse)")
+            if d.get("mlp_only_layers"):
+                raise ValueError(f"{name}: Qwen3-MoE with mlp_only_layers={d.get('mlp_only_layers')} is not "
+                                 f"supported (mixed dense / sparse layers)")
+            moe = dict(num_experts=int(ne), num_experts_per_tok=int(d["num_experts_per_tok"]),
+                       moe_intermediate_size=int(d["moe_intermediate_size"]),
+                       norm_topk_prob=bool(d.get("norm_topk_prob", False)))
+        if mt in ("qwen3", "qwen3_moe"):
             # every layer must attend over the whole context: a sliding-window layer served as a
             # full-attention one would be silently wrong
             if d.get("use_sliding_window"):
@@ -108,15 +138,17 @@ class ModelConfig:
         prf = d.get("partial_rotary_factor", rp.get("partial_rotary_factor", 1.0))
         rot = int(hd * prf) if prf and prf < 1.0 else None
         return ModelConfig(name=name, arch=arch, vocab_size=d["vocab_size"], hidden_size=H,
-                           intermediate_size=d["intermediate_size"], num_layers=d["num_hidden_layers"],
+                           intermediate_size=d.get("intermediate_size", 0) if moe else d["intermediate_size"],
+                           num_layers=d["num_hidden_layers"],
                            num_heads=nh, num_kv_heads=d.get("num_key_value_heads", nh),
                            head_dim=d.get("head_dim") or H // nh, rope_theta=float(theta),
                            rope_scaling=scaling, rms_eps=d.get("rms_norm_eps", 1e-5),
                            max_position=d.get("max_position_embeddings", 8192),
                            tie_embeddings=d.get("tie_word_embeddings", False),
                            qkv_bias=bool(d.get("attention_bias", mt == "qwen2")),
-                           rotary_dim=rot, rope_interleaved=(mt == "glm"), qk_norm=(mt == "qwen3"),
-                           bos_token_id=d.get("bos_token_id", 1), eos_token_id=eos)
+                           rotary_dim=rot, rope_interleaved=(mt == "glm"),
+                           qk_norm=(mt in ("qwen3", "qwen3_moe")), bos_token_id=d.get("bos_token_id", 1),
+                           eos_token_id=eos, **moe)
 
     @staticmethod
     def from_file(path: str) -> "ModelConfig":
@@ -177,6 +209,20 @@ PRESETS: dict[str, ModelConfig] = {
                               intermediate_size=2048, num_layers=2, num_heads=16, num_kv_heads=2, head_dim=128,
                               rope_theta=1000000.0, rms_eps=1e-6, max_position=4096, tie_embeddings=True,
                               qk_norm=True, bos_token_id=1, eos_token_id=2),
+    # Qwen3-MoE: the Qwen3 attention block with a top-k routed set of SwiGLU experts as every layer's
+    # MLP.  Qwen3-30B-A3B as its published config is remembered (not checkable offline; a local
+    # config.json takes precedence).  intermediate_size is the config's dense width, which no layer uses.
+    "qwen3-30b-a3b": ModelConfig(name="qwen3-30b-a3b", arch="qwen3_moe", vocab_size=151936, hidden_size=2048,
+                                 intermediate_size=6144, num_layers=48, num_heads=32, num_kv_heads=4, head_dim=128,
+                                 rope_theta=1000000.0, rms_eps=1e-6, max_position=40960, qk_norm=True,
+                                 bos_token_id=151643, eos_token_id=151645, num_experts=128,
+                                 num_experts_per_tok=8, moe_intermediate_size=768, norm_topk_prob=True),
+    # tiny Qwen3-MoE for tests: 8 experts of width 256, 2 per token
+    "qwen3-moe-tiny": ModelConfig(name="qwen3-moe-tiny", arch="qwen3_moe", vocab_size=1024, hidden_size=512,
+                                  intermediate_size=1024, num_layers=2, num_heads=8, num_kv_heads=2, head_dim=128,
+                                  rope_theta=1000000.0, rms_eps=1e-6, max_position=4096, qk_norm=True,
+                                  bos_token_id=1, eos_token_id=2, num_experts=8, num_experts_per_tok=2,
+                                  moe_intermediate_size=256, norm_topk_prob=True),
     # GLM-4-9B (HF "glm"): Llama block + biased QKV, GQA 16:1, half-dim interleaved RoPE
     "glm-4-9b": ModelConfig(name="glm-4-9b", arch="glm", vocab_size=151552, hidden_size=4096,
                             intermediate_size=13696, num_layers=40, num_heads=32, num_kv_heads=2, head_dim=128,
@@ -234,8 +280,10 @@ def get_config(name_or_path: str) -> ModelConfig:
             for size in ("0.6b", "32b", "8b"):
                 if re.search(rf"(?<![\d.]){re.escape(size)}(?![\d])", tail):
                     return dataclasses.replace(PRESETS["qwen3-" + size], name=name_or_path)
+        hint = " (Qwen3-30B-A3B is the preset 'qwen3-30b-a3b')" if re.search(r"30b-a3b", tail) else ""
         raise KeyError(f"unknown Qwen3 model {name_or_path!r}: presets exist for "
-                       f"{sorted(k for k in PRESETS if k.startswith('qwen3-'))}; pass a local config.json")
+                       f"{sorted(k for k in PRESETS if k.startswith('qwen3-'))}; pass a preset key or a local "
+                       f"config.json{hint}")
     if "qwen" in lk:
         return dataclasses.replace(PRESETS["qwen2.5-0.5b" if "0.5b" in lk else "qwen2.5-7b"], name=name_or_path)
     if "70b" in lk:

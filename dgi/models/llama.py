@@ -11,7 +11,8 @@ with fused QKV and gate|up weights so each layer issues 4 GEMMs.  Qwen2's biased
 q/k/v projections ride in the QKV GEMM's bias epilogue (hipBLASLt), so the
 family adds no kernel; GLM-4 adds biased QKV and half-dim interleaved RoPE
 (``rope_cache`` mode 1 over the first ``rotary_dim`` dims); Qwen3 drops the bias and
-normalises every q and k head before RoPE, inside the writer (``qknorm_rope_cache``).  A model
+normalises every q and k head before RoPE, inside the writer (``qknorm_rope_cache``); Qwen3-MoE
+replaces every layer's MLP by a top-k routed set of SwiGLU experts (``ops.moe_mlp``).  A model
 object may hold any contiguous layer range (pipeline stage): stage 0 owns the
 embedding, the last stage the final norm and LM head, exactly like the
 reference's ``ModelShard`` (model_shard.py:28-59).  Between stages a single
@@ -83,14 +84,19 @@ def _ss_cols(hidden: int) -> int:
 
 
 class LlamaLayerWeights:
-    __slots__ = ("in_norm", "qkv", "o", "post_norm", "gate_up", "down", "qkv_bias", "q_norm", "k_norm")
+    __slots__ = ("in_norm", "qkv", "o", "post_norm", "gate_up", "down", "qkv_bias", "q_norm", "k_norm",
+                 "router", "experts_gate_up", "experts_down")
 
-    def __init__(self, in_norm, qkv, o, post_norm, gate_up, down, qkv_bias=None, q_norm=None, k_norm=None):
+    def __init__(self, in_norm, qkv, o, post_norm, gate_up, down, qkv_bias=None, q_norm=None, k_norm=None,
+                 router=None, experts_gate_up=None, experts_down=None):
         self.in_norm, self.qkv, self.o = in_norm, qkv, o
         self.post_norm, self.gate_up, self.down = post_norm, gate_up, down
         self.qkv_bias = qkv_bias   # [qkv_size] for Qwen2, else None (fused into the QKV GEMM epilogue)
         # [head_dim] gains of the per-head q / k RMSNorm for Qwen3, else None (ops.qknorm_rope_cache)
         self.q_norm, self.k_norm = q_norm, k_norm
+        # MoE layers (Qwen3-MoE): router [E, H], experts' [gate; up] [E, 2I, H] and down [E, H, I];
+        # their gate_up and down are None (ops.moe_mlp)
+        self.router, self.experts_gate_up, self.experts_down = router, experts_gate_up, experts_down
 
 
 QUANT_SLOTS = ("qkv", "o", "gate_up", "down")    # the projections quantize_weights replaces
@@ -149,6 +155,9 @@ class LlamaModel:
         self.weight_quant: Optional[str] = None
         self.act_quant: Optional[str] = None        # "fp8": W8A8 above ops.W8A8_MIN_M rows (quantize_weights)
         self._quant_scratch: Optional[torch.Tensor] = None
+        # MoE models (tests): hook(global layer, positions, ids [T, k], weights [T, k]) -> ids to
+        # force, or None to keep the router's choice.  Eager steps only: it reads the routing
+        self.route_hook = None
         if checkpoint:
             # real weights: only this rank's layers / TP slices are read (dgi.models.weights)
             from dgi.models.weights import load_checkpoint
@@ -171,14 +180,19 @@ class LlamaModel:
     def _init_empty(self):
         c, dev, dt = self.cfg, self.device, self.dtype
         H, I = c.hidden_size, c.intermediate_size
+        E, Im = c.num_experts, c.moe_intermediate_size
         for _ in range(self.num_local_layers):
             self.layers.append(LlamaLayerWeights(
                 torch.ones(H, device=dev, dtype=dt), torch.empty(c.qkv_size, H, device=dev, dtype=dt),
                 torch.empty(H, c.q_size, device=dev, dtype=dt), torch.ones(H, device=dev, dtype=dt),
-                torch.empty(2 * I, H, device=dev, dtype=dt), torch.empty(H, I, device=dev, dtype=dt),
+                None if c.is_moe else torch.empty(2 * I, H, device=dev, dtype=dt),
+                None if c.is_moe else torch.empty(H, I, device=dev, dtype=dt),
                 torch.zeros(c.qkv_size, device=dev, dtype=dt) if c.qkv_bias else None,
                 torch.ones(c.head_dim, device=dev, dtype=dt) if c.qk_norm else None,
-                torch.ones(c.head_dim, device=dev, dtype=dt) if c.qk_norm else None))
+                torch.ones(c.head_dim, device=dev, dtype=dt) if c.qk_norm else None,
+                torch.empty(E, H, device=dev, dtype=dt) if c.is_moe else None,
+                torch.empty(E, 2 * Im, H, device=dev, dtype=dt) if c.is_moe else None,
+                torch.empty(E, H, Im, device=dev, dtype=dt) if c.is_moe else None))
         if self.has_embed:
             self.embed = torch.empty(c.vocab_size, H, device=dev, dtype=dt)
         if self.has_head:
@@ -202,15 +216,26 @@ class LlamaModel:
             qkv = _rand((c.qkv_size, H), gen, dev, dt, std)
             o = _rand((H, c.q_size), gen, dev, dt, std / math.sqrt(2 * c.num_layers))
             ln2 = 1.0 + 0.1 * _rand((H,), gen, dev, torch.float32, 1.0)
-            gu = _rand((2 * I, H), gen, dev, dt, std)
-            down = _rand((H, I), gen, dev, dt, std / math.sqrt(2 * c.num_layers))
+            gu = down = None
+            if not c.is_moe:
+                gu = _rand((2 * I, H), gen, dev, dt, std)
+                down = _rand((H, I), gen, dev, dt, std / math.sqrt(2 * c.num_layers))
             bias = _rand((c.qkv_size,), gen, dev, dt, std) if c.qkv_bias else None
             # drawn after every other tensor of the layer: models without the norm keep their weights
             qn = kn = None
             if c.qk_norm:
                 qn = (1.0 + 0.1 * _rand((c.head_dim,), gen, dev, torch.float32, 1.0)).to(dt)
                 kn = (1.0 + 0.1 * _rand((c.head_dim,), gen, dev, torch.float32, 1.0)).to(dt)
-            self.layers.append(LlamaLayerWeights(ln1.to(dt), qkv, o, ln2.to(dt), gu, down, bias, qn, kn))
+            # the router and the experts come last of all, so no dense model's weights move.  The
+            # router's std is large enough that the experts' logits are well apart after the norm
+            rt = egu = edn = None
+            if c.is_moe:
+                E, Im = c.num_experts, c.moe_intermediate_size
+                rt = _rand((E, H), gen, dev, dt, 4 * std)
+                egu = _rand((E, 2 * Im, H), gen, dev, dt, std)
+                edn = _rand((E, H, Im), gen, dev, dt, std / math.sqrt(2 * c.num_layers))
+            self.layers.append(LlamaLayerWeights(ln1.to(dt), qkv, o, ln2.to(dt), gu, down, bias, qn, kn,
+                                                 rt, egu, edn))
         if self.has_embed or (self.has_head and c.tie_embeddings):
             gen.manual_seed(seed * 1000003 + 17)
             emb = _rand((c.vocab_size, H), gen, dev, dt, 1.0)
@@ -263,6 +288,8 @@ class LlamaModel:
             raise ValueError(f"quantize_weights: unsupported mode {mode!r} (supported: 'fp8', 'mxfp4')")
         if act_quant not in (None, "fp8"):
             raise ValueError(f"quantize_weights: unsupported act_quant {act_quant!r} (supported: None, 'fp8')")
+        if self.cfg.is_moe:
+            raise ValueError(f"quantize_weights: {self.cfg.name} is a MoE model; quantised experts are not supported")
         if act_quant and mode != "fp8":
             raise ValueError(f"quantize_weights: act_quant={act_quant!r} needs mode='fp8' (the e4m3 GEMM reads "
                              f"e4m3 weights), not {mode!r}")
@@ -326,11 +353,14 @@ class LlamaModel:
                 L.q_norm.copy_(sd[p + "self_attn.q_norm.weight"])
                 L.k_norm.copy_(sd[p + "self_attn.k_norm.weight"])
             L.o.copy_(sd[p + "self_attn.o_proj.weight"])
-            if p + "mlp.gate_up_proj.weight" in sd:     # GLM: fused [gate; up]
+            if L.router is not None:
+                self._load_experts_hf(L, sd, p + "mlp.")
+            elif p + "mlp.gate_up_proj.weight" in sd:     # GLM: fused [gate; up]
                 L.gate_up.copy_(sd[p + "mlp.gate_up_proj.weight"])
             else:
                 L.gate_up.copy_(torch.cat([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]], 0))
-            L.down.copy_(sd[p + "mlp.down_proj.weight"])
+            if L.router is None:
+                L.down.copy_(sd[p + "mlp.down_proj.weight"])
             L.in_norm.copy_(sd[p + "input_layernorm.weight"])
             L.post_norm.copy_(sd[p + "post_attention_layernorm.weight"])
         if self.has_embed:
@@ -340,6 +370,27 @@ class LlamaModel:
             if "lm_head.weight" in sd and self.lm_head is not self.embed:
                 self.lm_head.copy_(sd["lm_head.weight"])
         del c
+
+    def _load_experts_hf(self, L: LlamaLayerWeights, sd: dict, m: str) -> None:
+        """A MoE layer's router and experts from HF names under ``m`` (``model.layers.N.mlp.``): the
+        fused in-memory tensors of transformers 5 (``experts.gate_up_proj [E, 2I, H]``,
+        ``experts.down_proj [E, H, I]``) or the published per-expert ``experts.{e}.{gate,up,down}_proj``.
+        A missing tensor is a KeyError that names it."""
+        def get(name):
+            if name not in sd:
+                raise KeyError(f"load_state_dict_hf: {self.cfg.arch} state dict without {name}")
+            return sd[name]
+        L.router.copy_(get(m + "gate.weight"))
+        if m + "experts.gate_up_proj" in sd:
+            L.experts_gate_up.copy_(sd[m + "experts.gate_up_proj"])
+            L.experts_down.copy_(get(m + "experts.down_proj"))
+            return
+        Im = self.cfg.moe_intermediate_size
+        for e in range(self.cfg.num_experts):
+            x = f"{m}experts.{e}."
+            L.experts_gate_up[e, :Im].copy_(get(x + "gate_proj.weight"))
+            L.experts_gate_up[e, Im:].copy_(get(x + "up_proj.weight"))
+            L.experts_down[e].copy_(get(x + "down_proj.weight"))
 
     def tensors(self):
         """(name, tensor) pairs of every weight (lm_head omitted when tied).  A quantised
@@ -378,7 +429,8 @@ class LlamaModel:
     def weight_bytes(self) -> int:
         n = 0
         for L in self.layers:
-            for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias, L.q_norm, L.k_norm):
+            for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias, L.q_norm, L.k_norm,
+                      L.router, L.experts_gate_up, L.experts_down):
                 if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight)):
                     n += t.nbytes()      # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements)
                 elif t is not None:
@@ -475,8 +527,24 @@ class LlamaModel:
         ops.fused_add_rmsnorm(h, residual, L.in_norm, self.cfg.rms_eps)
         return h, residual
 
+    def _mlp(self, i: int, L: LlamaLayerWeights, x: torch.Tensor, positions: torch.Tensor) -> torch.Tensor:
+        """Local layer ``i``'s MLP on the normalised rows ``x`` (the ``ops.linear`` route): dense
+        SwiGLU, or for a MoE layer the routed experts (``ops.moe_mlp``).  ``positions`` are the rows'
+        positions, for ``route_hook``."""
+        if L.router is None:
+            return ops.linear(ops.silu_mul(ops.linear(x, L.gate_up)), L.down)
+        c = self.cfg
+        k, norm = c.num_experts_per_tok, c.norm_topk_prob
+        ids = None
+        if self.route_hook is not None:
+            if x.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("route_hook is set during stream capture: it reads the routing, run eager steps")
+            chosen, weights = ops.moe_route(ops.linear(x, L.router), k, norm)
+            ids = self.route_hook(self.layer_start + i, positions, chosen, weights)
+        return ops.moe_mlp(x, L.router, L.experts_gate_up, L.experts_down, k, norm, ids=ids)
+
     def _trimmed_tail(self, i: int, L: LlamaLayerWeights, attn: torch.Tensor, stream: torch.Tensor,
-                      rows: torch.Tensor) -> tuple:
+                      rows: torch.Tensor, positions: Optional[torch.Tensor] = None) -> tuple:
         """The last layer after its attention (which has written every row's K/V), on the logits
         rows ``rows`` alone: o-proj, add + norm, MLP.  Returns (MLP output, stream) of those rows;
         nothing is recorded in ``captured`` (forward() never trims while layers are captured)."""
@@ -487,7 +555,7 @@ class LlamaModel:
         if self.reduce is not None:
             self.reduce(h)
         ops.fused_add_rmsnorm(h, stream, L.post_norm, eps)
-        h = ops.linear(ops.silu_mul(ops.linear(h, L.gate_up)), L.down)
+        h = self._mlp(i, L, h, None if positions is None else positions.index_select(0, rows))
         if self.reduce is not None:
             self.reduce(h)
         if self.layer_hook is not None:
@@ -660,6 +728,10 @@ class LlamaModel:
             return self._forward_layers_quant(h, meta, residual, trim_last)
         if not self.layers:
             return h, residual
+        if self.cfg.is_moe:
+            # the unfused loop, always: the fused-norm, fused-decode and MFMA-table layers read the
+            # dense gate_up / down a MoE layer does not have
+            return self._unfused_layers(h, meta, residual, trim_last, T)
         if self._fold_ok(h):
             return self._forward_layers_folded(h, meta, residual, trim_last)
         fq, fg = self._fused_decode(h, meta)
@@ -693,7 +765,7 @@ class LlamaModel:
                 qkv = ops.linear(h, L.qkv, L.qkv_bias)
             attn = self.attention(i, qkv, meta)
             if trim_last is not None and i == len(self.layers) - 1:
-                return self._trimmed_tail(i, L, attn, residual, trim_last)
+                return self._trimmed_tail(i, L, attn, residual, trim_last, meta.positions)
             if Mp > T:
                 # o-proj writes the first T rows of the padded MLP input
                 h = ops.mfma_gemm(attn, L.o, 0, out=self._pad_buf[:T]) if mfma_o else \
@@ -704,8 +776,11 @@ class LlamaModel:
                 self.reduce(h)
             ops.fused_add_rmsnorm(h, residual, L.post_norm, eps)
             x = self._pad_buf[:Mp] if Mp > T else h
-            act = ops.mfma_gemm(x, L.gate_up, 1) if mfma_gu else ops.silu_mul(ops.linear(x, L.gate_up))
-            h = ops.mfma_gemm(act, L.down, 0) if mfma_dn else ops.linear(act, L.down)
+            if mfma_gu or mfma_dn:
+                act = ops.mfma_gemm(x, L.gate_up, 1) if mfma_gu else ops.silu_mul(ops.linear(x, L.gate_up))
+                h = ops.mfma_gemm(act, L.down, 0) if mfma_dn else ops.linear(act, L.down)
+            else:
+                h = self._mlp(i, L, x, meta.positions)
             if Mp > T:
                 h = h[:T]
             if self.reduce is not None:

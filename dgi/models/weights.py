@@ -169,17 +169,34 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
             n += 2
         _put(L.o, rd.read(a + "o_proj.weight", cols=q_rows) if tp > 1 else rd.read(a + "o_proj.weight"))
         m = p + "mlp."
-        if m + "gate_up_proj.weight" in rd:        # GLM-4: fused [gate; up]
+        if L.router is not None:
+            # Qwen3-MoE: the published per-expert tensors, each read straight into its slice of the
+            # stacked [E, 2I, H] / [E, H, I] weights (never a CPU copy of a whole layer's experts)
+            Im = c.moe_intermediate_size
+            names = [m + "gate.weight"] + [f"{m}experts.{e}.{k}_proj.weight" for e in range(c.num_experts)
+                                           for k in ("gate", "up", "down")]
+            for name in names:
+                if name not in rd:
+                    raise KeyError(f"{path}: {c.arch} checkpoint without {name}")
+            _put(L.router, rd.read(names[0]))
+            for e in range(c.num_experts):
+                x = f"{m}experts.{e}."
+                _put(L.experts_gate_up[e, :Im], rd.read(x + "gate_proj.weight"))
+                _put(L.experts_gate_up[e, Im:], rd.read(x + "up_proj.weight"))
+                _put(L.experts_down[e], rd.read(x + "down_proj.weight"))
+            n += 1 + 3 * c.num_experts
+        elif m + "gate_up_proj.weight" in rd:        # GLM-4: fused [gate; up]
             I = full.intermediate_size
             _put(L.gate_up[:Il], rd.read(m + "gate_up_proj.weight", rows=i_rows))
             _put(L.gate_up[Il:], rd.read(m + "gate_up_proj.weight", rows=(I + i_rows[0], I + i_rows[1])))
         else:
             _put(L.gate_up[:Il], rd.read(m + "gate_proj.weight", rows=i_rows))
             _put(L.gate_up[Il:], rd.read(m + "up_proj.weight", rows=i_rows))
-        _put(L.down, rd.read(m + "down_proj.weight", cols=i_rows) if tp > 1 else rd.read(m + "down_proj.weight"))
+        if L.router is None:
+            _put(L.down, rd.read(m + "down_proj.weight", cols=i_rows) if tp > 1 else rd.read(m + "down_proj.weight"))
         _put(L.in_norm, rd.read(p + "input_layernorm.weight"))
         _put(L.post_norm, rd.read(p + "post_attention_layernorm.weight"))
-        n += 6
+        n += 3 if L.router is not None else 6     # o and the two norms; dense: gate, up and down as well
     if model.embed is not None:
         _put(model.embed, rd.read("model.embed_tokens.weight"))
         n += 1

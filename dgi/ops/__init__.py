@@ -1226,6 +1226,240 @@ def topk(logits: torch.Tensor, k: int):
 
 
 # ----------------------------------------------------------------------------
+# Mixture of experts (moe.hip): router, expert-sorted layout, grouped GEMM, combine
+# ----------------------------------------------------------------------------
+# A token's k experts occupy the flat slots t*k + j (j in descending logit order).  The sorted
+# layout groups the slots by expert, ascending slot inside an expert, each expert padded to the
+# grouped GEMM's row block BM; P rows hold any assignment of n slots to E experts.
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOPK = 16
+MOE_EPI_PLAIN, MOE_EPI_SWIGLU = 0, 1
+
+
+def moe_capacity(n: int, E: int, BM: int) -> int:
+    """Rows of the sorted layout of ``n`` slots over ``E`` experts with row blocks of ``BM``."""
+    return BM * ((n + BM - 1) // BM + min(E, n))
+
+
+def moe_block_rows(T: int, k: int, E: int) -> int:
+    """Row block of the grouped GEMM for a step: 32 once an expert averages more than 16 rows."""
+    return 32 if T * k > 16 * E else 16
+
+
+def _route_weights(logits: torch.Tensor, ids: torch.Tensor, norm: bool) -> torch.Tensor:
+    """fp32 softmax probabilities of ``logits`` at ``ids``: exp(l - max) over the chosen sum
+    (``norm``) or over the full sum."""
+    lf = logits.float()
+    m = lf.max(-1, keepdim=True).values
+    p = torch.exp(lf.gather(-1, ids.long()) - m)
+    den = p.sum(-1, keepdim=True) if norm else torch.exp(lf - m).sum(-1, keepdim=True)
+    return p / den
+
+
+def moe_route_ref(logits: torch.Tensor, k: int, norm: bool):
+    """The definition of ``moe_route``: the k largest LOGITS per row in descending order, ties to
+    the lower expert index (a stable sort), and their fp32 softmax weights."""
+    order = torch.sort(-logits.float(), dim=-1, stable=True).indices
+    ids = order[:, :k].to(torch.int32)
+    return ids, _route_weights(logits, ids, norm)
+
+
+def _moe_route_native(logits: torch.Tensor, k: int) -> bool:
+    E = logits.shape[-1]
+    return (logits.is_cuda and logits.dim() == 2 and logits.dtype in (torch.bfloat16, torch.float32)
+            and logits.stride(1) == 1 and E <= MOE_MAX_EXPERTS and 1 <= k <= min(E, MOE_MAX_TOPK))
+
+
+def moe_route(logits: torch.Tensor, k: int, norm: bool):
+    """Router logits ``[T, E]`` (bf16 or fp32) -> ``ids [T, k]`` int32, ``weights [T, k]`` fp32."""
+    if not 1 <= k <= logits.shape[-1]:
+        raise ValueError(f"moe_route: k={k} outside 1..E={logits.shape[-1]}")
+    if _moe_route_native(logits, k) and logits.shape[0] > 0:
+        load_native(required=True)
+        T = logits.shape[0]
+        ids = torch.empty(T, k, dtype=torch.int32, device=logits.device)
+        w = torch.empty(T, k, dtype=torch.float32, device=logits.device)
+        _call("moe_route", ids, w, logits, k, bool(norm))
+        return ids, w
+    return moe_route_ref(logits, k, norm)
+
+
+def moe_align_ref(ids: torch.Tensor, E: int, BM: int):
+    """The definition of ``moe_align``: (counts [E], offsets [E + 1], sorted_slot [P],
+    block_expert [P / BM], inv [n]), all int32.  Slots are grouped by expert in ascending slot
+    order (a stable sort), expert e starts at the BM-padded ``offsets[e]``; padding rows and the
+    unused tail hold -1."""
+    flat = ids.reshape(-1).long()
+    n = flat.numel()
+    P = moe_capacity(n, E, BM)
+    dev = flat.device
+    counts = torch.bincount(flat, minlength=E)[:E]
+    padded = (counts + BM - 1) // BM * BM
+    ends = torch.cumsum(padded, 0)
+    offsets = torch.cat([ends.new_zeros(1), ends])
+    order = torch.sort(flat, stable=True).indices            # slots by expert, ascending inside one
+    first = torch.cumsum(counts, 0) - counts                  # unpadded start of each expert
+    ex = flat[order]
+    pos = offsets[ex] + (torch.arange(n, device=dev) - first[ex])
+    sorted_slot = torch.full((P,), -1, dtype=torch.int32, device=dev)
+    sorted_slot[pos] = order.to(torch.int32)
+    inv = torch.empty(n, dtype=torch.int32, device=dev)
+    inv[order] = pos.to(torch.int32)
+    be = torch.searchsorted(ends, torch.arange(P // BM, device=dev) * BM, right=True)
+    block_expert = torch.where(be < E, be, torch.full_like(be, -1)).to(torch.int32)
+    return counts.to(torch.int32), offsets.to(torch.int32), sorted_slot, block_expert, inv
+
+
+def moe_align(ids: torch.Tensor, E: int, BM: int):
+    """Expert-sorted layout of the routing ``ids`` (int32, ``[T, k]`` or flat); see ``moe_align_ref``."""
+    if BM not in (16, 32):
+        raise ValueError(f"moe_align: BM must be 16 or 32, got {BM}")
+    if ids.is_cuda and ids.dtype == torch.int32 and E <= MOE_MAX_EXPERTS and ids.numel() > 0:
+        load_native(required=True)
+        flat = ids.reshape(-1).contiguous()
+        n = flat.numel()
+        P = moe_capacity(n, E, BM)
+        mk = lambda m: torch.empty(m, dtype=torch.int32, device=ids.device)     # noqa: E731
+        counts, offsets, sorted_slot, block_expert, inv = mk(E), mk(E + 1), mk(P), mk(P // BM), mk(n)
+        _call("moe_align", counts, offsets, sorted_slot, block_expert, inv, flat, E, BM)
+        return counts, offsets, sorted_slot, block_expert, inv
+    return moe_align_ref(ids, E, BM)
+
+
+def _silu_mul_f32(gu: torch.Tensor) -> torch.Tensor:
+    I = gu.shape[-1] // 2
+    return torch.nn.functional.silu(gu[..., :I]) * gu[..., I:]
+
+
+def moe_gemm_ref(x: torch.Tensor, w: torch.Tensor, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
+                 epi: int, BM: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The definition of ``moe_gemm``: row p of row block b is ``A[p] · w[block_expert[b]]^T`` with
+    fp32 accumulation, rounded once to ``x.dtype``.  SwiGLU (``epi`` 1, ``w = [gate; up]``): A[p] is
+    token ``sorted_slot[p] // k`` of ``x`` and the fp32 ``silu(gate) * up`` is what is rounded; plain:
+    A[p] is row p of ``x``.  Padding rows (slot -1) are left as ``out`` had them (zeros without ``out``)."""
+    P = sorted_slot.numel()
+    N = w.shape[1] // 2 if epi else w.shape[1]
+    if out is None:
+        out = torch.zeros(P, N, dtype=x.dtype, device=x.device)
+    row_e = block_expert.long().repeat_interleave(BM)
+    slot = sorted_slot.long()
+    for e in torch.unique(row_e[slot >= 0]).tolist():
+        rows = torch.nonzero((row_e == e) & (slot >= 0)).flatten()
+        a = x[slot[rows] // k] if epi else x[rows]
+        y = a.float() @ w[e].float().t()
+        out[rows] = (_silu_mul_f32(y) if epi else y).to(out.dtype)
+    return out
+
+
+def _moe_gemm_native(x: torch.Tensor, w: torch.Tensor, epi: int) -> bool:
+    N = w.shape[1] // 2 if epi else w.shape[1]
+    return (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 3
+            and x.stride(1) == 1 and x.stride(0) % 8 == 0 and w.is_contiguous() and x.shape[1] % 256 == 0
+            and N % 16 == 0 and w.shape[0] <= MOE_MAX_EXPERTS and x.data_ptr() % 16 == 0)
+
+
+def moe_gemm(x: torch.Tensor, w: torch.Tensor, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
+             epi: int, BM: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Grouped GEMM over the sorted layout (``moe_align``): ``[P, N]`` in sorted order.  ``epi``
+    ``MOE_EPI_SWIGLU`` gathers token rows of ``x [T, K]`` and applies SwiGLU over ``w [E, 2N, K]``;
+    ``MOE_EPI_PLAIN`` reads ``x [P, K]`` in sorted order against ``w [E, N, K]``.  ``k`` is the experts
+    per token (the slot -> token divisor).  The HIP kernel takes bf16, K % 256 == 0, N % 16 == 0."""
+    if _moe_gemm_native(x, w, epi):
+        load_native(required=True)
+        P = sorted_slot.numel()
+        N = w.shape[1] // 2 if epi else w.shape[1]
+        if out is None:
+            out = torch.empty(P, N, dtype=x.dtype, device=x.device)
+        nslots = x.shape[0] * k if epi else P
+        _call("moe_gemm", out, x, w, sorted_slot, block_expert, k, nslots, epi, BM)
+        return out
+    return moe_gemm_ref(x, w, sorted_slot, block_expert, k, epi, BM, out)
+
+
+def moe_combine_ref(y: torch.Tensor, inv: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """The definition of ``moe_combine``: ``out[t] = round(sum_j weights[t, j] * float(y[inv[t*k + j]]))``,
+    each product rounded to fp32, added in j order, one final rounding to ``y.dtype``.  A slot with
+    ``inv < 0`` contributes nothing."""
+    T, k = weights.shape
+    rows = inv.reshape(T, k).long()
+    acc = torch.zeros(T, y.shape[1], dtype=torch.float32, device=y.device)
+    for j in range(k):
+        r = rows[:, j]
+        term = weights[:, j, None].float() * y[r.clamp_min(0)].float()
+        acc = acc + torch.where((r >= 0)[:, None], term, torch.zeros_like(term))
+    return acc.to(y.dtype)
+
+
+def moe_combine(y: torch.Tensor, inv: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """Weighted sum of each token's k expert outputs ``y [P, H]`` (sorted order) -> ``[T, H]``."""
+    if (y.is_cuda and y.dtype == torch.bfloat16 and y.is_contiguous() and y.shape[1] % 8 == 0
+            and weights.dtype == torch.float32 and weights.shape[1] <= MOE_MAX_TOPK and inv.dtype == torch.int32):
+        load_native(required=True)
+        out = torch.empty(weights.shape[0], y.shape[1], dtype=y.dtype, device=y.device)
+        _call("moe_combine", out, y, inv.contiguous(), weights.contiguous())
+        return out
+    return moe_combine_ref(y, inv, weights)
+
+
+def moe_mlp_ref(x: torch.Tensor, router_w: torch.Tensor, gate_up: torch.Tensor, down: torch.Tensor, k: int,
+                norm_topk: bool, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The definition of ``moe_mlp``, as the per-expert loop: router logits ``x @ router_w^T`` in
+    ``x.dtype``, ``moe_route_ref`` (or the forced ``ids`` with the model's own probabilities at them),
+    then for every expert its tokens through ``silu(gate) * up`` (fp32, rounded to ``x.dtype``) and
+    ``down`` (fp32 accumulate, rounded), combined by ``moe_combine_ref``."""
+    T, H = x.shape
+    logits = torch.nn.functional.linear(x, router_w)
+    if ids is None:
+        ids, weights = moe_route_ref(logits, k, norm_topk)
+    else:
+        ids = ids.to(torch.int32)
+        weights = _route_weights(logits, ids, norm_topk)
+    flat = ids.reshape(-1).long()
+    y = torch.zeros(T * k, H, dtype=x.dtype, device=x.device)
+    for e in torch.unique(flat).tolist():
+        slots = torch.nonzero(flat == e).flatten()
+        a = x[slots // k].float()
+        act = _silu_mul_f32(a @ gate_up[e].float().t()).to(x.dtype)
+        y[slots] = (act.float() @ down[e].float().t()).to(x.dtype)
+    inv = torch.arange(T * k, dtype=torch.int32, device=x.device)
+    return moe_combine_ref(y, inv, weights)
+
+
+def moe_mlp_ok(x: torch.Tensor, router_w: torch.Tensor, gate_up: torch.Tensor, down: torch.Tensor, k: int) -> bool:
+    """Whether the HIP kernels take this MoE block (else ``moe_mlp`` is ``moe_mlp_ref``)."""
+    E, I2, H = gate_up.shape
+    return (x.is_cuda and x.dim() == 2 and x.shape[0] > 0 and x.dtype == torch.bfloat16
+            and gate_up.dtype == torch.bfloat16 and down.dtype == torch.bfloat16
+            and gate_up.is_contiguous() and down.is_contiguous() and H % 256 == 0 and (I2 // 2) % 256 == 0
+            and E <= MOE_MAX_EXPERTS and 1 <= k <= min(E, MOE_MAX_TOPK) and x.shape[0] * k < (1 << 30))
+
+
+def moe_mlp(x: torch.Tensor, router_w: torch.Tensor, gate_up: torch.Tensor, down: torch.Tensor, k: int,
+            norm_topk: bool, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Top-k routed SwiGLU experts (no shared expert): ``x [T, H]``, ``router_w [E, H]``,
+    ``gate_up [E, 2I, H]`` (``[gate; up]`` per expert), ``down [E, H, I]`` -> ``[T, H]``.  On the
+    GPU: the router through ``linear``, then ``moe_route`` -> ``moe_align`` -> ``moe_gemm`` (SwiGLU)
+    -> ``moe_gemm`` (plain) -> ``moe_combine``; nothing is read back, so the block captures into a
+    graph.  ``ids`` forces the routing (tests): the weights are then the model's own softmax
+    probabilities at those ids."""
+    if not moe_mlp_ok(x, router_w, gate_up, down, k):
+        return moe_mlp_ref(x, router_w, gate_up, down, k, norm_topk, ids)
+    T = x.shape[0]
+    E = gate_up.shape[0]
+    logits = linear(x, router_w)
+    if ids is None:
+        ids, weights = moe_route(logits, k, norm_topk)
+    else:
+        ids = ids.to(device=x.device, dtype=torch.int32).contiguous()
+        weights = _route_weights(logits, ids, norm_topk)
+    BM = moe_block_rows(T, k, E)
+    _counts, _offsets, sorted_slot, block_expert, inv = moe_align(ids, E, BM)
+    act = moe_gemm(x, gate_up, sorted_slot, block_expert, k, MOE_EPI_SWIGLU, BM)
+    y = moe_gemm(act, down, sorted_slot, block_expert, k, MOE_EPI_PLAIN, BM)
+    return moe_combine(y, inv, weights)
+
+
+# ----------------------------------------------------------------------------
 # KV block movement
 # ----------------------------------------------------------------------------
 

@@ -33,6 +33,9 @@ from dgi.models.llama import LlamaLayerWeights, LlamaModel, _rand
 
 
 def tp_local_config(cfg: ModelConfig, tp: int) -> ModelConfig:
+    if cfg.is_moe:
+        raise ValueError(f"{cfg.name}: tensor parallelism of a MoE model is not supported (expert and tensor "
+                         f"parallelism of the experts are non-goals); serve it with LLMEngine on one GPU")
     if cfg.num_heads % tp or cfg.num_kv_heads % tp or cfg.intermediate_size % tp:
         raise ValueError(f"{cfg.name}: heads {cfg.num_heads}/{cfg.num_kv_heads} and intermediate "
                          f"{cfg.intermediate_size} must be divisible by tp={tp}")

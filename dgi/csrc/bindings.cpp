@@ -380,49 +380,52 @@ void moe_combine(at::Tensor out, const at::Tensor& y, const at::Tensor& inv, con
            "moe_combine");
 }
 
+// What the three weight-streaming GEMMs ask of out [M, N], x [M, K] and the optional bias [N], given
+// the [N, K] of the weight: the kernels read x in 16-byte vectors and write M <= 32 rows.  Returns the
+// bias pointer (nullptr for none).
+const void* check_skinny_operands(const char* name, const at::Tensor& out, const at::Tensor& x, int64_t N, int64_t K,
+                                  const c10::optional<at::Tensor>& bias) {
+  check_bf16(out, "out"); check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, name, ": 2-D operands");
+  TORCH_CHECK(x.stride(1) == 1 && out.stride(1) == 1, name, ": row-major operands");
+  TORCH_CHECK(x.device() == out.device(), name, ": operands on one device");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, name, ": shape mismatch");
+  TORCH_CHECK(M <= 32 && K % 1024 == 0 && N % 16 == 0 && x.stride(0) % 8 == 0, name, ": M<=32, K%1024, N%16");
+  TORCH_CHECK((M <= 1 || x.stride(0) >= K) && (M <= 1 || out.stride(0) >= N), name, ": overlapping rows");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, name, ": x 16-byte aligned");
+  if (!bias.has_value()) return nullptr;
+  check_bf16(*bias, "bias");
+  TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == x.device(), name, ": bias [N]");
+  return bias->data_ptr();
+}
+
 void skinny_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w,
                  const c10::optional<at::Tensor>& bias, int64_t cfg) {
-  check_bf16(out, "out"); check_bf16(x, "x"); check_bf16(w, "w");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "skinny_gemm: 2-D operands");
-  TORCH_CHECK(x.stride(1) == 1 && out.stride(1) == 1 && w.is_contiguous(), "skinny_gemm: row-major operands");
-  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "skinny_gemm: shape mismatch");
-  TORCH_CHECK(M <= 32 && K % 1024 == 0 && N % 16 == 0 && x.stride(0) % 8 == 0, "skinny_gemm: M<=32, K%1024, N%16");
-  const void* b = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N);
-    b = bias->data_ptr();
-  }
+  check_bf16(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous() && w.device() == x.device() && (uintptr_t)w.data_ptr() % 16 == 0,
+              "skinny_gemm: w row-major, 16-byte aligned, on x's device");
+  const int64_t N = w.size(0), K = w.size(1);
+  const void* b = check_skinny_operands("skinny_gemm", out, x, N, K, bias);
   check_rc(dgi_skinny_gemm(x.data_ptr(), (int)x.stride(0), w.data_ptr(), b, out.data_ptr(), (int)out.stride(0),
-                           (int)M, (int)N, (int)K, (int)cfg, cur_stream()),
+                           (int)x.size(0), (int)N, (int)K, (int)cfg, cur_stream()),
            "skinny_gemm");
 }
 
 // W8A16 decode GEMM: out = (x wq^T) * scale (+ bias); wq [N, K] OCP e4m3, scale [N] fp32 per output channel.
 void skinny_gemm_w8(at::Tensor out, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale,
                     const c10::optional<at::Tensor>& bias, int64_t cfg) {
-  check_bf16(out, "out"); check_bf16(x, "x"); check_dev(wq, "wq"); check_dev(scale, "scale");
+  check_dev(wq, "wq"); check_dev(scale, "scale");
   TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn, "skinny_gemm_w8: wq must be float8_e4m3fn");
   TORCH_CHECK(scale.scalar_type() == at::kFloat, "skinny_gemm_w8: scale must be float32");
-  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2, "skinny_gemm_w8: 2-D operands");
-  TORCH_CHECK(x.stride(1) == 1 && out.stride(1) == 1 && wq.is_contiguous() && scale.is_contiguous(),
-              "skinny_gemm_w8: row-major operands");
-  TORCH_CHECK(x.device() == wq.device() && x.device() == out.device() && x.device() == scale.device(),
-              "skinny_gemm_w8: operands on one device");
-  const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
-  TORCH_CHECK(wq.size(1) == K && out.size(0) == M && out.size(1) == N && scale.numel() == N,
-              "skinny_gemm_w8: shape mismatch");
-  TORCH_CHECK(M <= 32 && K % 1024 == 0 && N % 16 == 0 && x.stride(0) % 8 == 0,
-              "skinny_gemm_w8: M<=32, K%1024, N%16");
-  const void* b = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N);
-    b = bias->data_ptr();
-  }
+  TORCH_CHECK(wq.dim() == 2 && wq.is_contiguous() && scale.is_contiguous() && scale.numel() == wq.size(0),
+              "skinny_gemm_w8: wq row-major [N, K], scale [N]");
+  TORCH_CHECK(wq.device() == x.device() && scale.device() == x.device(), "skinny_gemm_w8: operands on one device");
+  TORCH_CHECK((uintptr_t)wq.data_ptr() % 16 == 0, "skinny_gemm_w8: wq 16-byte aligned");
+  const int64_t N = wq.size(0), K = wq.size(1);
+  const void* b = check_skinny_operands("skinny_gemm_w8", out, x, N, K, bias);
   check_rc(dgi_skinny_gemm_w8(x.data_ptr(), (int)x.stride(0), wq.data_ptr(), scale.data_ptr(), b, out.data_ptr(),
-                              (int)out.stride(0), (int)M, (int)N, (int)K, (int)cfg, cur_stream()),
+                              (int)out.stride(0), (int)x.size(0), (int)N, (int)K, (int)cfg, cur_stream()),
            "skinny_gemm_w8");
 }
 
@@ -446,32 +449,19 @@ void dequant_fp8(at::Tensor out, const at::Tensor& wq, const at::Tensor& scale) 
 // first), scale [N, K/32] e8m0 bytes, one per 32 elements of a row.
 void skinny_gemm_w4(at::Tensor out, const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale,
                     const c10::optional<at::Tensor>& bias, int64_t cfg) {
-  check_bf16(out, "out"); check_bf16(x, "x"); check_dev(q, "q"); check_dev(scale, "scale");
+  check_dev(q, "q"); check_dev(scale, "scale");
   TORCH_CHECK(q.scalar_type() == at::kByte, "skinny_gemm_w4: q must be uint8");
   TORCH_CHECK(scale.scalar_type() == at::kByte, "skinny_gemm_w4: scale must be uint8 (e8m0)");
-  TORCH_CHECK(x.dim() == 2 && q.dim() == 2 && scale.dim() == 2 && out.dim() == 2, "skinny_gemm_w4: 2-D operands");
-  TORCH_CHECK(x.stride(1) == 1 && out.stride(1) == 1 && q.is_contiguous() && scale.is_contiguous(),
-              "skinny_gemm_w4: row-major operands");
-  TORCH_CHECK(x.device() == q.device() && x.device() == out.device() && x.device() == scale.device(),
-              "skinny_gemm_w4: operands on one device");
-  const int64_t M = x.size(0), K = x.size(1), N = q.size(0);
-  TORCH_CHECK(M <= 32 && K % 1024 == 0 && N % 16 == 0 && x.stride(0) % 8 == 0,
-              "skinny_gemm_w4: M<=32, K%1024, N%16");
-  TORCH_CHECK(q.size(1) == K / 2 && scale.size(0) == N && scale.size(1) == K / 32 && out.size(0) == M &&
-                  out.size(1) == N,
-              "skinny_gemm_w4: shape mismatch");
-  TORCH_CHECK((M <= 1 || x.stride(0) >= K) && (M <= 1 || out.stride(0) >= N), "skinny_gemm_w4: overlapping rows");
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)q.data_ptr() % 16 == 0 &&
-                  (uintptr_t)scale.data_ptr() % 2 == 0,
-              "skinny_gemm_w4: x and q 16-byte aligned, scale 2-byte aligned");
-  const void* b = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == x.device());
-    b = bias->data_ptr();
-  }
+  TORCH_CHECK(q.dim() == 2 && scale.dim() == 2 && q.is_contiguous() && scale.is_contiguous(),
+              "skinny_gemm_w4: q and scale row-major 2-D");
+  TORCH_CHECK(q.device() == x.device() && scale.device() == x.device(), "skinny_gemm_w4: operands on one device");
+  const int64_t N = q.size(0), K = 2 * q.size(1);
+  TORCH_CHECK(scale.size(0) == N && scale.size(1) * 32 == K, "skinny_gemm_w4: scale must be [N, K/32]");
+  TORCH_CHECK((uintptr_t)q.data_ptr() % 16 == 0 && (uintptr_t)scale.data_ptr() % 2 == 0,
+              "skinny_gemm_w4: q 16-byte aligned, scale 2-byte aligned");
+  const void* b = check_skinny_operands("skinny_gemm_w4", out, x, N, K, bias);
   check_rc(dgi_skinny_gemm_w4(x.data_ptr(), (int)x.stride(0), q.data_ptr(), scale.data_ptr(), b, out.data_ptr(),
-                              (int)out.stride(0), (int)M, (int)N, (int)K, (int)cfg, cur_stream()),
+                              (int)out.stride(0), (int)x.size(0), (int)N, (int)K, (int)cfg, cur_stream()),
            "skinny_gemm_w4");
 }
 

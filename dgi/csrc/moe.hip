@@ -11,12 +11,10 @@
 //                 its slots (first launch), then places them in ascending slot order by ballot /
 //                 popcount prefixes (second launch).  Every expert's rows are padded to the GEMM's
 //                 row block BM; padding rows carry slot -1, unused row blocks expert -1.
-//  * moe_gemm     Y[row block b] = X[rows of b] · W[block_expert[b]]^T.  The skinny_gemm.hip
-//                 design (see its header): weights straight to VGPRs with nontemporal loads, lane
-//                 l holds the B fragment of v_mfma_f32_16x16x32_bf16 for weight row n0 + (l & 15),
-//                 the waves of a workgroup split K and sum through LDS.  The SwiGLU epilogue
-//                 gathers its A rows through sorted_slot / k and owns the same column range of
-//                 gate and of up; the plain epilogue reads act in sorted order.  At large T an
+//  * moe_gemm     Y[row block b] = X[rows of b] · W[block_expert[b]]^T on the weight-streaming
+//                 core of stream_gemm.h.  The SwiGLU epilogue gathers its A rows through
+//                 sorted_slot / k and owns the same column range of gate and of up; the plain
+//                 epilogue reads act in sorted order.  At large T an
 //                 expert's weights are read once per row block (an LDS-tiled prefill kernel is
 //                 future work).
 //  * moe_combine  out[t] = bf16(sum_j weights[t, j] * y[inv[t*k + j]]): fp32, j order, no FMA
@@ -24,7 +22,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "stream_gemm.h"
 
 using namespace dgi;
 
@@ -185,15 +183,10 @@ __global__ __launch_bounds__(kAlignThreads) void moe_place_kernel(
 }
 
 // ---------------------------------------------------------------- grouped GEMM
-template <int MT, int WT>
-struct Frag {
-  u32x4 w[WT][2];
-  u32x4 x[MT][2];
-};
-
 __device__ __forceinline__ float silu(float g) { return g / (1.f + expf(-g)); }
 
-// NW waves split K in 64-deep steps (step s belongs to wave s % NW); D groups in flight per wave.
+// stream_gemm.h's core over bf16 weights in 64-deep steps, one step per group.  Row block
+// blockIdx.y multiplies the 16·MT sorted rows p0.. by expert block_expert[blockIdx.y].
 // SWIGLU: W is [E, 2N, K] and the block multiplies rows n0.. of gate and N + n0.. of up.
 template <int NW, int MT, int NT, int D, bool SWIGLU>
 __global__ __launch_bounds__(NW * 64) void moe_gemm_kernel(
@@ -201,114 +194,37 @@ __global__ __launch_bounds__(NW * 64) void moe_gemm_kernel(
     const int* __restrict__ block_expert, uint16_t* __restrict__ Y, int ldy, int N, int K, int kdiv, int nslots,
     int E) {
   constexpr int WT = SWIGLU ? 2 * NT : NT;
-  __shared__ f32x4 red[NW][MT * WT][64];
   const int e = block_expert[blockIdx.y];
   if (e < 0 || e >= E) return;  // unused row block (workgroup-uniform)
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int r = lane & 15;
-  const int g = lane >> 4;
   const int n0 = blockIdx.x * 16 * NT;
   const int p0 = blockIdx.y * 16 * MT;
-  const int ngroups = (K >> 6) / NW;  // host: K % (64 * NW) == 0
   const size_t wrows = SWIGLU ? 2 * (size_t)N : (size_t)N;
-  const uint16_t* wbase = W + (size_t)e * wrows * K + g * 16 + (size_t)w * 64;
-  const uint16_t* wrow[WT];
+  stream_gemm<Bf16W, NW, MT, WT, NT, 1, D>(
+      X, ldx, K,  // host: K % (64 * NW) == 0
+      [&](int m) {
+        const int slot = sorted_slot[p0 + m];
+        if (slot < 0 || slot >= nslots) return -1;  // padding rows read nothing
+        // SwiGLU gathers the token's row; the plain epilogue reads act in sorted order
+        return kdiv > 0 ? slot / kdiv : p0 + m;
+      },
+      [&](int t, int r, int g, int w) {
+        return Bf16W::ptr(W, (size_t)e * wrows + ((t < NT ? 0 : N) + n0 + (t % NT) * 16 + r), K, g, w);
+      },
+      [&](int mt, int nt, int r, int g, auto tile) {
+        const f32x4 a = tile(nt);
+        f32x4 u = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (SWIGLU) u = tile(NT + nt);
+        const int col = n0 + nt * 16 + r;
 #pragma unroll
-  for (int t = 0; t < WT; ++t) {
-    const int row = (t < NT ? 0 : N) + n0 + (t % NT) * 16 + r;
-    wrow[t] = wbase + (size_t)row * K;
-  }
-  const uint16_t* xrow[MT];
-  bool xval[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int p = p0 + mt * 16 + r;
-    const int slot = sorted_slot[p];
-    xval[mt] = slot >= 0 && slot < nslots;
-    // SwiGLU gathers the token's row; the plain epilogue reads act in sorted order
-    const int row = xval[mt] ? (kdiv > 0 ? slot / kdiv : p) : 0;
-    xrow[mt] = X + (size_t)row * ldx + g * 16 + w * 64;
-  }
-  f32x4 acc[MT][WT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int t = 0; t < WT; ++t) acc[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  auto load = [&](Frag<MT, WT>& f, int grp) {
-    const size_t off = (size_t)grp * NW * 64;
-#pragma unroll
-    for (int t = 0; t < WT; ++t) {
-      const u32x4* p = reinterpret_cast<const u32x4*>(wrow[t] + off);
-      f.w[t][0] = __builtin_nontemporal_load(p);
-      f.w[t][1] = __builtin_nontemporal_load(p + 1);
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      if (xval[mt]) {
-        const u32x4* p = reinterpret_cast<const u32x4*>(xrow[mt] + off);
-        f.x[mt][0] = p[0];
-        f.x[mt][1] = p[1];
-      } else {  // padding rows read nothing
-        f.x[mt][0] = u32x4{0u, 0u, 0u, 0u};
-        f.x[mt][1] = u32x4{0u, 0u, 0u, 0u};
-      }
-    }
-  };
-  auto compute = [&](const Frag<MT, WT>& f) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int t = 0; t < WT; ++t) {
-        acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[mt][0]), as_bf16x8(f.w[t][0]),
-                                                            acc[mt][t], 0, 0, 0);
-        acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[mt][1]), as_bf16x8(f.w[t][1]),
-                                                            acc[mt][t], 0, 0, 0);
-      }
-  };
-  Frag<MT, WT> ring[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-    if (d < ngroups) load(ring[d], d);
-  for (int base = 0; base < ngroups; base += D) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      if (base + d < ngroups) {  // uniform
-        compute(ring[d]);
-        if (base + D + d < ngroups) load(ring[d], base + D + d);
-      }
-    }
-  }
-
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int t = 0; t < WT; ++t) red[w][mt * WT + t][lane] = acc[mt][t];
-  __syncthreads();
-  // wave w sums the NW partial tiles of output tile w, w + NW, ... in wave order
-  for (int o = w; o < MT * NT; o += NW) {
-    const int mt = o / NT, nt = o % NT;
-    f32x4 a = red[0][mt * WT + nt][lane];
-#pragma unroll
-    for (int j = 1; j < NW; ++j) a += red[j][mt * WT + nt][lane];
-    f32x4 u = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (SWIGLU) {
-      u = red[0][mt * WT + NT + nt][lane];
-#pragma unroll
-      for (int j = 1; j < NW; ++j) u += red[j][mt * WT + NT + nt][lane];
-    }
-    const int col = n0 + nt * 16 + r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int p = p0 + mt * 16 + g * 4 + i;
-      const int slot = sorted_slot[p];
-      if (slot >= 0 && slot < nslots) {  // padding rows write nothing
-        const float val = SWIGLU ? silu(a[i]) * u[i] : a[i];
-        Y[(size_t)p * ldy + col] = f32_to_bf16(val);
-      }
-    }
-  }
+        for (int i = 0; i < 4; ++i) {
+          const int p = p0 + mt * 16 + g * 4 + i;
+          const int slot = sorted_slot[p];
+          if (slot >= 0 && slot < nslots) {  // padding rows write nothing
+            const float val = SWIGLU ? silu(a[i]) * u[i] : a[i];
+            Y[(size_t)p * ldy + col] = f32_to_bf16(val);
+          }
+        }
+      });
 }
 
 template <int MT, bool SWIGLU>

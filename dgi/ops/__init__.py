@@ -509,6 +509,49 @@ def _env_cfg(name: str, unset: int, table: dict) -> int:
     return cfg
 
 
+def _skinny_takes(x: torch.Tensor) -> bool:
+    """Whether the weight-streaming kernels (skinny_gemm, _w8, _w4) read this [M, K] activation: bf16 on the
+    GPU in 16-byte vectors, rows that do not overlap."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.stride(1) == 1 and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0 and (x.shape[0] == 1 or x.stride(0) >= x.shape[1]))
+
+
+def _skinny_run(op: str, x: torch.Tensor, N: int, out: Optional[torch.Tensor], *args) -> torch.Tensor:
+    """``op(r, x, *args)`` for an activation that ``_skinny_takes``: ``r`` is the caller's ``out`` where the
+    kernel can write it directly ([M, N] bf16 rows on the GPU), else a fresh buffer copied back."""
+    M = x.shape[0]
+    load_native(required=True)
+    direct = (out is not None and out.dtype == torch.bfloat16 and out.shape == (M, N) and out.is_cuda
+              and out.stride(1) == 1 and (M == 1 or out.stride(0) >= N))
+    r = out if direct else torch.empty(M, N, dtype=x.dtype, device=x.device)
+    _call(op, r, x, *args)
+    return r if direct or out is None else out.copy_(r)
+
+
+def _skinny_cfg_ok(table: dict, default_cfg: int, step: int, cfg: int, N: int, K: int) -> bool:
+    """Whether launch config ``cfg`` (0: the default) of a ``table`` over ``step``-deep K steps divides [N, K]."""
+    nw, nt, u, _d = table[cfg or default_cfg]
+    return K % 1024 == 0 and N % (16 * nt) == 0 and (K // step) % (nw * u) == 0
+
+
+def _use_skinny_quant(M: int, N: int, K: int) -> bool:
+    """The quantised formats take every decode-sized step their kernel can launch."""
+    return 0 < M <= min(32, SKINNY_MAX_M) and K % 1024 == 0 and N % 16 == 0
+
+
+def _dequant(op: str, w, out: Optional[torch.Tensor]) -> torch.Tensor:
+    N, K = w.shape
+    if out is None or out.numel() < N * K or out.device != w.device or out.dtype != torch.bfloat16:
+        out = torch.empty(N * K, dtype=torch.bfloat16, device=w.device)
+    out = out.view(-1)[: N * K].view(N, K)
+    if w.q.is_cuda:
+        load_native(required=True)
+        _call(op, out, w.q, w.scale)     # K % 16 (fp8) or % 32 (mxfp4) == 0, checked by the op
+    else:
+        out.copy_(w.dequant(torch.bfloat16))
+    return out
+
+
 # launch configs of skinny_gemm: cfg -> (waves per workgroup, column tiles per wave, 64-deep K steps
 # per load group, ring depth); 0 runs 4.  cfg 5 runs two column tiles at M > 16.  _skinny_cfg selects
 # 4 and 5; the others are sweep points (profiles/r1_skinny_gemm.md), of which 3 and 6 are retired.
@@ -532,13 +575,12 @@ def _skinny_cfg(M: int, N: int) -> int:
 # (K / 128) % (waves * steps) == 0
 SKINNY_W8_CFGS = {1: (8, 1, 1, 4), 2: (8, 1, 1, 2), 3: (4, 1, 2, 2), 4: (4, 1, 2, 4), 5: (8, 2, 1, 2),
                   6: (4, 1, 1, 8), 7: (16, 1, 1, 2), 8: (8, 4, 1, 2)}
-SKINNY_W8_CFG = int(os.environ.get("DGI_SKINNY_W8_CFG", "0"))    # > 0 forces a launch config (sweeps)
+SKINNY_W8_CFG = _env_cfg("DGI_SKINNY_W8_CFG", 0, SKINNY_W8_CFGS)    # > 0 forces a launch config (sweeps)
 
 
 def skinny_w8_cfg_ok(cfg: int, N: int, K: int) -> bool:
     """Whether launch config ``cfg`` of ``skinny_gemm_w8`` divides an [N, K] weight."""
-    nw, nt, u, _d = SKINNY_W8_CFGS[cfg or 2]
-    return K % 1024 == 0 and N % (16 * nt) == 0 and (K // 128) % (nw * u) == 0
+    return _skinny_cfg_ok(SKINNY_W8_CFGS, 2, 128, cfg, N, K)
 
 
 def _skinny_w8_cfg(M: int, N: int) -> int:
@@ -557,10 +599,6 @@ def _skinny_w8_cfg(M: int, N: int) -> int:
     return 8 if (M > 8 and N >= 16384) else 5
 
 
-def _use_skinny_w8(M: int, N: int, K: int) -> bool:
-    return 0 < M <= min(32, SKINNY_MAX_M) and K % 1024 == 0 and N % 16 == 0
-
-
 def linear_fp8_ref(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     return torch.nn.functional.linear(x.float(), w.q.float() * w.scale[:, None],
                                       None if bias is None else bias.float()).to(x.dtype)
@@ -568,16 +606,7 @@ def linear_fp8_ref(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor] =
 
 def dequant_fp8(w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [N, K] copy of an fp8 weight; ``out``: a flat bf16 buffer of >= N*K elements."""
-    N, K = w.shape
-    if out is None or out.numel() < N * K or out.device != w.device or out.dtype != torch.bfloat16:
-        out = torch.empty(N * K, dtype=torch.bfloat16, device=w.device)
-    out = out.view(-1)[: N * K].view(N, K)
-    if w.q.is_cuda:
-        load_native(required=True)
-        _call("dequant_fp8", out, w.q, w.scale)     # K % 16 == 0, checked by the op
-    else:
-        out.copy_(w.dequant(torch.bfloat16))
-    return out
+    return _dequant("dequant_fp8", w, out)
 
 
 # FP8 W8A8 projections (mfma_gemm_fp8.hip): an opt-in mode on top of the fp8 weights
@@ -672,12 +701,8 @@ def _linear_fp8(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor], out
         N = w.shape[0]
         if w8a8 and _w8a8_fits(x, w, bias):
             return linear_w8a8(x, w, bias, out)
-        if _use_skinny_w8(M, N, K) and x.stride(1) == 1 and x.stride(0) % 8 == 0:
-            load_native(required=True)
-            if out is None:
-                out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-            _call("skinny_gemm_w8", out, x, w.q, w.scale, bias, _skinny_w8_cfg(M, N))
-            return out
+        if _use_skinny_quant(M, N, K) and _skinny_takes(x):
+            return _skinny_run("skinny_gemm_w8", x, N, out, w.q, w.scale, bias, _skinny_w8_cfg(M, N))
         r = torch.nn.functional.linear(x, dequant_fp8(w, w.scratch), bias)
     elif w8a8:
         r = linear_w8a8_ref(x, w, bias)
@@ -706,8 +731,7 @@ SKINNY_W4_CFG = _env_cfg("DGI_SKINNY_W4_CFG", 0, SKINNY_W4_CFGS)    # > 0 forces
 
 def skinny_w4_cfg_ok(cfg: int, N: int, K: int) -> bool:
     """Whether launch config ``cfg`` of ``skinny_gemm_w4`` divides an [N, K] weight."""
-    nw, nt, u, _d = SKINNY_W4_CFGS[cfg or 2]
-    return K % 1024 == 0 and N % (16 * nt) == 0 and (K // 256) % (nw * u) == 0
+    return _skinny_cfg_ok(SKINNY_W4_CFGS, 2, 256, cfg, N, K)
 
 
 def _skinny_w4_cfg(M: int, N: int, K: int = 0) -> int:
@@ -731,10 +755,6 @@ def _skinny_w4_cfg(M: int, N: int, K: int = 0) -> int:
     return 5
 
 
-def _use_skinny_w4(M: int, N: int, K: int) -> bool:
-    return 0 < M <= min(32, SKINNY_MAX_M) and K % 1024 == 0 and N % 16 == 0
-
-
 def linear_mxfp4_ref(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     return torch.nn.functional.linear(x.float(), w.dequant(torch.float32),
                                       None if bias is None else bias.float()).to(x.dtype)
@@ -742,33 +762,16 @@ def linear_mxfp4_ref(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tenso
 
 def dequant_mxfp4(w: Mxfp4Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [N, K] copy of an mxfp4 weight (exact); ``out``: a flat bf16 buffer of >= N*K elements."""
-    N, K = w.shape
-    if out is None or out.numel() < N * K or out.device != w.device or out.dtype != torch.bfloat16:
-        out = torch.empty(N * K, dtype=torch.bfloat16, device=w.device)
-    out = out.view(-1)[: N * K].view(N, K)
-    if w.q.is_cuda:
-        load_native(required=True)
-        _call("dequant_mxfp4", out, w.q, w.scale)     # K % 32 == 0 by construction, checked by the op
-    else:
-        out.copy_(w.dequant(torch.bfloat16))
-    return out
+    return _dequant("dequant_mxfp4", w, out)
 
 
 def _linear_mxfp4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor], out: Optional[torch.Tensor]):
     if x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16:
         M, K = x.shape
         N = w.shape[0]
-        if (_use_skinny_w4(M, N, K) and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
-                and (M == 1 or x.stride(0) >= K)):
-            load_native(required=True)
-            direct = (out is not None and out.dtype == torch.bfloat16 and out.shape == (M, N) and out.is_cuda
-                      and out.stride(1) == 1 and (M == 1 or out.stride(0) >= N))
-            r = out if direct else torch.empty(M, N, dtype=x.dtype, device=x.device)
-            _call("skinny_gemm_w4", r, x, w.q, w.scale, bias, _skinny_w4_cfg(M, N, K))
-            if direct:
-                return out
-        else:
-            r = torch.nn.functional.linear(x, dequant_mxfp4(w, w.scratch), bias)
+        if _use_skinny_quant(M, N, K) and _skinny_takes(x):
+            return _skinny_run("skinny_gemm_w4", x, N, out, w.q, w.scale, bias, _skinny_w4_cfg(M, N, K))
+        r = torch.nn.functional.linear(x, dequant_mxfp4(w, w.scratch), bias)
     else:
         r = linear_mxfp4_ref(x, w, bias)
     if out is not None:
@@ -789,13 +792,9 @@ def linear(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None,
         return torch.nn.functional.linear(x, w, bias)
     M, K = x.shape
     N = w.shape[0]
-    if (x.is_cuda and _use_skinny(M, N, K) and x.dtype == torch.bfloat16
-            and w.dtype == torch.bfloat16 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and w.is_contiguous()):
-        load_native(required=True)
-        if out is None:
-            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        _call("skinny_gemm", out, x, w, bias, _skinny_cfg(M, N))
-        return out
+    if (_use_skinny(M, N, K) and _skinny_takes(x) and w.dtype == torch.bfloat16 and w.is_contiguous()
+            and w.data_ptr() % 16 == 0):
+        return _skinny_run("skinny_gemm", x, N, out, w, bias, _skinny_cfg(M, N))
     r = torch.nn.functional.linear(x, w, bias)
     if out is not None:
         out.copy_(r)

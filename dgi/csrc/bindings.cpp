@@ -88,6 +88,9 @@ int dgi_moe_align(const int* ids, int n, int E, int BM, int P, int* counts, int*
                   int* block_expert, int* inv, hipStream_t s);
 int dgi_moe_gemm(const void* x, int ldx, const void* w, const int* sorted_slot, const int* block_expert, void* y,
                  int ldy, int P, int N, int K, int kdiv, int nslots, int E, int BM, int epi, hipStream_t s);
+int dgi_moe_gemm_w8(const void* x, int ldx, const void* q, const float* scale, const int* sorted_slot,
+                    const int* block_expert, void* y, int ldy, int P, int N, int K, int kdiv, int nslots, int E, int BM,
+                    int epi, hipStream_t s);
 int dgi_moe_combine(const void* y, int ldy, const int* inv, const float* weights, void* out, int T, int k, int H,
                     int P, hipStream_t s);
 }
@@ -362,6 +365,42 @@ void moe_gemm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, const at
                         block_expert.data_ptr<int>(), out.data_ptr(), (int)out.stride(0), (int)P, (int)N, (int)K,
                         epi ? (int)k : 0, (int)nslots, (int)E, (int)BM, (int)epi, cur_stream()),
            "moe_gemm");
+}
+
+// moe_gemm over FP8 weight-only experts: q [E, N or 2N, K] float8_e4m3fn codes, scale [E, N or 2N] fp32;
+// out = bf16((x · q[e]^T) * scale[e]), for SwiGLU gate and up scaled before silu(gate) * up.
+void moe_gemm_w8(at::Tensor out, const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale,
+                 const at::Tensor& sorted_slot, const at::Tensor& block_expert, int64_t k, int64_t nslots, int64_t epi,
+                 int64_t BM) {
+  check_bf16(out, "out"); check_bf16(x, "x"); check_dev(q, "q"); check_dev(scale, "scale");
+  check_i32(sorted_slot, "sorted_slot"); check_i32(block_expert, "block_expert");
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn, "moe_gemm_w8: q must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "moe_gemm_w8: scale must be float32");
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 3 && scale.dim() == 2 && out.dim() == 2,
+              "moe_gemm_w8: x and out 2-D, q 3-D, scale 2-D");
+  TORCH_CHECK(x.stride(1) == 1 && out.is_contiguous() && q.is_contiguous() && scale.is_contiguous(),
+              "moe_gemm_w8: row-major operands");
+  TORCH_CHECK(epi == 0 || epi == 1, "moe_gemm_w8: epi 0 (plain) or 1 (SwiGLU)");
+  TORCH_CHECK(BM == 16 || BM == 32, "moe_gemm_w8: BM 16 or 32");
+  const int64_t P = sorted_slot.numel(), K = x.size(1), E = q.size(0), N = out.size(1);
+  TORCH_CHECK(P % BM == 0 && block_expert.numel() == P / BM && out.size(0) == P, "moe_gemm_w8: layout sizes");
+  TORCH_CHECK(q.size(2) == K && q.size(1) == (epi ? 2 * N : N), "moe_gemm_w8: shape mismatch");
+  TORCH_CHECK(scale.size(0) == E && scale.size(1) == q.size(1), "moe_gemm_w8: scale must be [E, rows of q]");
+  TORCH_CHECK(K % 256 == 0 && N % 16 == 0 && E >= 1 && E <= 256 && x.stride(0) % 8 == 0,
+              "moe_gemm_w8: K%256, N%16, E<=256");
+  TORCH_CHECK(k >= 1 && nslots >= 1 && nslots < (1ll << 30), "moe_gemm_w8: k and nslots");
+  // every row the kernel can follow lies inside x
+  TORCH_CHECK(epi ? (nslots - 1) / k < x.size(0) : x.size(0) == P,
+              "moe_gemm_w8: x needs nslots / k rows (SwiGLU) or the sorted layout's P rows (plain)");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)q.data_ptr() % 16 == 0 &&
+                  (uintptr_t)scale.data_ptr() % 16 == 0, "moe_gemm_w8: 16-byte alignment");
+  for (const at::Tensor* t : {&x, &q, &scale, &sorted_slot, &block_expert})
+    TORCH_CHECK(t->device() == out.device(), "moe_gemm_w8: one device");
+  check_rc(dgi_moe_gemm_w8(x.data_ptr(), (int)x.stride(0), q.data_ptr(), scale.data_ptr<float>(),
+                           sorted_slot.data_ptr<int>(), block_expert.data_ptr<int>(), out.data_ptr(),
+                           (int)out.stride(0), (int)P, (int)N, (int)K, epi ? (int)k : 0, (int)nslots, (int)E, (int)BM,
+                           (int)epi, cur_stream()),
+           "moe_gemm_w8");
 }
 
 // out [T, H] = bf16(sum_j weights[t, j] * y[inv[t*k + j]]), y [P, H]
@@ -924,6 +963,8 @@ TORCH_LIBRARY(dgi, m) {
         "Tensor(e!) inv, Tensor ids, int E, int BM) -> ()");
   m.def("moe_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor sorted_slot, Tensor block_expert, int k, int nslots, "
         "int epi, int BM) -> ()");
+  m.def("moe_gemm_w8(Tensor(a!) out, Tensor x, Tensor q, Tensor scale, Tensor sorted_slot, Tensor block_expert, "
+        "int k, int nslots, int epi, int BM) -> ()");
   m.def("moe_combine(Tensor(a!) out, Tensor y, Tensor inv, Tensor weights) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
   m.def("skinny_gemm_w8(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");
@@ -969,6 +1010,7 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("moe_route", &moe_route);
   m.impl("moe_align", &moe_align);
   m.impl("moe_gemm", &moe_gemm);
+  m.impl("moe_gemm_w8", &moe_gemm_w8);
   m.impl("moe_combine", &moe_combine);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("skinny_gemm_w8", &skinny_gemm_w8);

@@ -17,10 +17,17 @@
 //                 epilogue reads act in sorted order.  At large T an
 //                 expert's weights are read once per row block (an LDS-tiled prefill kernel is
 //                 future work).
+//  * moe_gemm_w8  the same kernel over FP8 weight-only experts (opt-in, expert_quant="fp8"): OCP
+//                 e4m3 codes [E, N or 2N, K] with one fp32 scale per expert and output channel,
+//                 widened in registers (E4m3W, 128-deep K steps).  The epilogue multiplies the fp32
+//                 sum by scale[e, col] (gate and up each by their own) before SwiGLU and the one
+//                 rounding.  4 waves split K when K % 512 == 0, else 2: a function of K alone, so
+//                 a row's bits do not depend on the row block.
 //  * moe_combine  out[t] = bf16(sum_j weights[t, j] * y[inv[t*k + j]]): fp32, j order, no FMA
 //                 contraction (the torch reference multiplies, rounds, adds), one final rounding.
 #include <limits.h>
 #include <math.h>
+#include <type_traits>
 
 #include "stream_gemm.h"
 
@@ -185,22 +192,26 @@ __global__ __launch_bounds__(kAlignThreads) void moe_place_kernel(
 // ---------------------------------------------------------------- grouped GEMM
 __device__ __forceinline__ float silu(float g) { return g / (1.f + expf(-g)); }
 
-// stream_gemm.h's core over bf16 weights in 64-deep steps, one step per group.  Row block
-// blockIdx.y multiplies the 16·MT sorted rows p0.. by expert block_expert[blockIdx.y].
+// stream_gemm.h's core over the weights of format F, one K step per group: 64 deep for bf16
+// (Bf16W), 128 deep for e4m3 codes (E4m3W, widened in registers as skinny_gemm_fp8.hip does).
+// Row block blockIdx.y multiplies the 16·MT sorted rows p0.. by expert block_expert[blockIdx.y].
 // SWIGLU: W is [E, 2N, K] and the block multiplies rows n0.. of gate and N + n0.. of up.
-template <int NW, int MT, int NT, int D, bool SWIGLU>
+// E4m3W: scale [E, N or 2N] fp32, one per expert and output channel; the fp32 tile sum is
+// multiplied by it (gate and up each by their own row's) before the epilogue's one rounding.
+template <class F, int NW, int MT, int NT, int D, bool SWIGLU>
 __global__ __launch_bounds__(NW * 64) void moe_gemm_kernel(
-    const uint16_t* __restrict__ X, int ldx, const uint16_t* __restrict__ W, const int* __restrict__ sorted_slot,
-    const int* __restrict__ block_expert, uint16_t* __restrict__ Y, int ldy, int N, int K, int kdiv, int nslots,
-    int E) {
+    const uint16_t* __restrict__ X, int ldx, typename F::Mat W, const float* __restrict__ scale,
+    const int* __restrict__ sorted_slot, const int* __restrict__ block_expert, uint16_t* __restrict__ Y, int ldy,
+    int N, int K, int kdiv, int nslots, int E) {
   constexpr int WT = SWIGLU ? 2 * NT : NT;
+  constexpr bool SCALED = !std::is_same<F, Bf16W>::value;
   const int e = block_expert[blockIdx.y];
   if (e < 0 || e >= E) return;  // unused row block (workgroup-uniform)
   const int n0 = blockIdx.x * 16 * NT;
   const int p0 = blockIdx.y * 16 * MT;
   const size_t wrows = SWIGLU ? 2 * (size_t)N : (size_t)N;
-  stream_gemm<Bf16W, NW, MT, WT, NT, 1, D>(
-      X, ldx, K,  // host: K % (64 * NW) == 0
+  stream_gemm<F, NW, MT, WT, NT, 1, D>(
+      X, ldx, K,  // host: K % (F::kStep * NW) == 0
       [&](int m) {
         const int slot = sorted_slot[p0 + m];
         if (slot < 0 || slot >= nslots) return -1;  // padding rows read nothing
@@ -208,13 +219,22 @@ __global__ __launch_bounds__(NW * 64) void moe_gemm_kernel(
         return kdiv > 0 ? slot / kdiv : p0 + m;
       },
       [&](int t, int r, int g, int w) {
-        return Bf16W::ptr(W, (size_t)e * wrows + ((t < NT ? 0 : N) + n0 + (t % NT) * 16 + r), K, g, w);
+        return F::ptr(W, (size_t)e * wrows + ((t < NT ? 0 : N) + n0 + (t % NT) * 16 + r), K, g, w);
       },
       [&](int mt, int nt, int r, int g, auto tile) {
-        const f32x4 a = tile(nt);
+        f32x4 a = tile(nt);
         f32x4 u = f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (SWIGLU) u = tile(NT + nt);
         const int col = n0 + nt * 16 + r;
+        if constexpr (SCALED) {
+          const float sa = scale[(size_t)e * wrows + col];
+          const float su = SWIGLU ? scale[(size_t)e * wrows + N + col] : 0.f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            a[i] *= sa;
+            u[i] *= su;
+          }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int p = p0 + mt * 16 + g * 4 + i;
@@ -233,11 +253,40 @@ int launch_gemm(const void* x, int ldx, const void* w, const int* sorted_slot, c
   constexpr int NW = 4, NT = 1;
   constexpr int D = MT == 1 ? 4 : 2;
   const dim3 grid(N / (16 * NT), P / (16 * MT));
-  moe_gemm_kernel<NW, MT, NT, D, SWIGLU><<<grid, NW * 64, 0, s>>>(
-      (const uint16_t*)x, ldx, (const uint16_t*)w, sorted_slot, block_expert, (uint16_t*)y, ldy, N, K, kdiv, nslots,
-      E);
+  moe_gemm_kernel<Bf16W, NW, MT, NT, D, SWIGLU><<<grid, NW * 64, 0, s>>>(
+      (const uint16_t*)x, ldx, (const uint16_t*)w, nullptr, sorted_slot, block_expert, (uint16_t*)y, ldy, N, K, kdiv,
+      nslots, E);
   DGI_CHECK_LAUNCH();
   return 0;
+}
+
+// e4m3 experts: NW waves split K's 128-deep steps, so NW is a function of K alone (the core's
+// results depend on NW, not on MT or D: a row's bits must not change with the row block).
+template <int NW, int MT, bool SWIGLU>
+int launch_gemm_w8(const void* x, int ldx, const void* q, const float* scale, const int* sorted_slot,
+                   const int* block_expert, void* y, int ldy, int P, int N, int K, int kdiv, int nslots, int E,
+                   hipStream_t s) {
+  constexpr int NT = 1;
+  // a double buffer at both row blocks: the deeper ring of the bf16 kernel's MT = 1 was 5-7 % slower
+  // here at T = 4 .. 64 (profiles/moe_fp8/README.md)
+  constexpr int D = 2;
+  const dim3 grid(N / (16 * NT), P / (16 * MT));
+  moe_gemm_kernel<E4m3W, NW, MT, NT, D, SWIGLU><<<grid, NW * 64, 0, s>>>(
+      (const uint16_t*)x, ldx, (const uint8_t*)q, scale, sorted_slot, block_expert, (uint16_t*)y, ldy, N, K, kdiv,
+      nslots, E);
+  DGI_CHECK_LAUNCH();
+  return 0;
+}
+
+template <int NW>
+int dispatch_gemm_w8(const void* x, int ldx, const void* q, const float* scale, const int* sorted_slot,
+                     const int* block_expert, void* y, int ldy, int P, int N, int K, int kdiv, int nslots, int E,
+                     int BM, int epi, hipStream_t s) {
+#define DGI_MOE_W8(MT, SW) \
+  launch_gemm_w8<NW, MT, SW>(x, ldx, q, scale, sorted_slot, block_expert, y, ldy, P, N, K, kdiv, nslots, E, s)
+  if (BM == 16) return epi ? DGI_MOE_W8(1, true) : DGI_MOE_W8(1, false);
+  return epi ? DGI_MOE_W8(2, true) : DGI_MOE_W8(2, false);
+#undef DGI_MOE_W8
 }
 
 // ---------------------------------------------------------------- combine
@@ -304,6 +353,22 @@ extern "C" int dgi_moe_gemm(const void* x, int ldx, const void* w, const int* so
                : launch_gemm<1, false>(x, ldx, w, sorted_slot, block_expert, y, ldy, P, N, K, kdiv, nslots, E, s);
   return epi ? launch_gemm<2, true>(x, ldx, w, sorted_slot, block_expert, y, ldy, P, N, K, kdiv, nslots, E, s)
              : launch_gemm<2, false>(x, ldx, w, sorted_slot, block_expert, y, ldy, P, N, K, kdiv, nslots, E, s);
+}
+
+// dgi_moe_gemm over e4m3 experts: q [E, N or 2N, K] OCP e4m3 codes, scale [E, N or 2N] fp32; the
+// result is bf16((x · q[e]^T) * scale[e]) (SwiGLU: gate and up scaled before silu(g) * u).
+// 4 waves when K % 512 == 0, else 2 (K = 768 is six 128-deep steps).
+extern "C" int dgi_moe_gemm_w8(const void* x, int ldx, const void* q, const float* scale, const int* sorted_slot,
+                               const int* block_expert, void* y, int ldy, int P, int N, int K, int kdiv, int nslots,
+                               int E, int BM, int epi, hipStream_t s) {
+  if (P <= 0 || N <= 0) return 0;
+  if (K % 256 || N % 16 || ldx % 8 || K <= 0) return -3;
+  if ((BM != 16 && BM != 32) || P % BM || E < 1 || E > kMaxExperts || kdiv < 0 || (epi != 0 && epi != 1)) return -3;
+  if (P / 16 > 65535) return -2;
+  if (K % 512 == 0)
+    return dispatch_gemm_w8<4>(x, ldx, q, scale, sorted_slot, block_expert, y, ldy, P, N, K, kdiv, nslots, E, BM, epi,
+                               s);
+  return dispatch_gemm_w8<2>(x, ldx, q, scale, sorted_slot, block_expert, y, ldy, P, N, K, kdiv, nslots, E, BM, epi, s);
 }
 
 // out [T, H] = bf16(sum_j weights[t, j] * y[inv[t*k + j]])

@@ -1,5 +1,6 @@
 // dgi/csrc/stream_gemm.h — the K-split register-ring core of the weight-streaming GEMMs
-// (skinny_gemm.hip, skinny_gemm_fp8.hip, skinny_gemm_mxfp4.hip and moe_gemm in moe.hip).
+// (skinny_gemm.hip, skinny_gemm_fp8.hip, skinny_gemm_mxfp4.hip, and moe_gemm / moe_gemm_w8 in
+// moe.hip: the grouped kernel over Bf16W and over E4m3W).
 //
 // Y[M, N] = X[M, K] · W[N, K]^T for decode-sized M.  At these sizes every projection is a read
 // of its weight matrix: the FLOPs are free and the kernel's job is to keep HBM3E streaming.

@@ -27,6 +27,7 @@ from dgi.utils.trace import phase
 
 WEIGHT_QUANT_MODES = (None, "fp8", "mxfp4")
 ACT_QUANT_MODES = (None, "fp8")       # "fp8": W8A8 on top of weight_quant="fp8"
+EXPERT_QUANT_MODES = (None, "fp8")    # FP8 weight-only experts of a MoE model (``LlamaModel.quantize_experts``)
 KV_DTYPES = (None, "fp8")      # None: KV pages in the activation dtype; "fp8": e4m3 codes + per-head scales
 logger = logging.getLogger(__name__)
 
@@ -37,6 +38,14 @@ def refuse_fp8_kv(cfg, what: str) -> None:
     if getattr(cfg, "kv_dtype", None) == "fp8":
         raise ValueError(f"kv_dtype='fp8' is not supported with {what}: serve it from a single-GPU "
                          "LLMEngine, or leave kv_dtype unset for a bf16 KV cache")
+
+
+def refuse_expert_quant(cfg, what: str) -> None:
+    """FP8 experts are served by the single-GPU engine only, as MoE models themselves are measured;
+    the multi-rank layouts refuse the knob at configuration time (``what`` names the layout)."""
+    if getattr(cfg, "expert_quant", None):
+        raise ValueError(f"expert_quant={cfg.expert_quant!r} is not supported with {what}: serve it from a "
+                         "single-GPU LLMEngine, or leave expert_quant unset for bf16 experts")
 
 
 def _refuse_fp8_kv_layout(model) -> None:
@@ -79,6 +88,8 @@ class EngineConfig:
                                          # e4m3 GEMM for steps of >= ops.W8A8_MIN_M rows (a token's numerics then
                                          # depend on its step's row count)
     kv_dtype: Optional[str] = None       # "fp8": e4m3 KV pages with per-head scales (``BlockPool.kv_scale``)
+    expert_quant: Optional[str] = None   # MoE models: "fp8" — weight-only e4m3 experts with per-expert, per-channel
+                                         # scales (``LlamaModel.quantize_experts``); everything else stays bf16
 
     def __post_init__(self):
         if self.kv_dtype not in KV_DTYPES:
@@ -90,6 +101,9 @@ class EngineConfig:
         if self.act_quant not in ACT_QUANT_MODES:
             raise ValueError(f"EngineConfig.act_quant={self.act_quant!r}: supported values are "
                              f"{', '.join(repr(m) for m in ACT_QUANT_MODES)}")
+        if self.expert_quant not in EXPERT_QUANT_MODES:
+            raise ValueError(f"EngineConfig.expert_quant={self.expert_quant!r}: supported values are "
+                             f"{', '.join(repr(m) for m in EXPERT_QUANT_MODES)}")
         if self.act_quant == "fp8" and self.weight_quant != "fp8":
             raise ValueError("EngineConfig.act_quant='fp8' needs weight_quant='fp8' (W8A8 runs on the fp8 weights)")
 
@@ -163,7 +177,10 @@ class LLMEngine:
         self.model_cfg.max_position = max(self.model_cfg.max_position, cfg.max_model_len)
         if cfg.weight_quant and self.model_cfg.is_moe:
             raise ValueError(f"EngineConfig.weight_quant={cfg.weight_quant!r}: {self.model_cfg.name} is a MoE model; "
-                             f"quantised experts are not supported")
+                             f"its projections stay bf16 (expert_quant='fp8' quantises its experts)")
+        if cfg.expert_quant and not self.model_cfg.is_moe:
+            raise ValueError(f"EngineConfig.expert_quant={cfg.expert_quant!r}: {self.model_cfg.name} is a dense model "
+                             f"(weight_quant quantises its projections)")
         t0 = time.perf_counter()
         self.model = model or LlamaModel(self.model_cfg, self.device, cfg.dtype, cfg.layer_start, cfg.layer_end,
                                          seed=cfg.seed, checkpoint=self.checkpoint)
@@ -171,6 +188,9 @@ class LLMEngine:
                                  or getattr(self.model, "act_quant", None) != cfg.act_quant):
             # before the KV budget: the pool gets the HBM the bf16 projections give back
             self.model.quantize_weights(cfg.weight_quant, act_quant=cfg.act_quant)
+        if cfg.expert_quant and getattr(self.model, "expert_quant", None) != cfg.expert_quant:
+            # before the KV budget: the pool gets the HBM the bf16 experts give back
+            self.model.quantize_experts(cfg.expert_quant)
         if self.device.type == "cuda":
             torch.cuda.synchronize()
         self.load_seconds = time.perf_counter() - t0

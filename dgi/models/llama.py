@@ -100,6 +100,7 @@ class LlamaLayerWeights:
 
 
 QUANT_SLOTS = ("qkv", "o", "gate_up", "down")    # the projections quantize_weights replaces
+EXPERT_SLOTS = ("experts_gate_up", "experts_down")    # the tensors quantize_experts replaces
 
 
 def _rand(shape, gen, device, dtype, std):
@@ -155,6 +156,8 @@ class LlamaModel:
         self.weight_quant: Optional[str] = None
         self.act_quant: Optional[str] = None        # "fp8": W8A8 above ops.W8A8_MIN_M rows (quantize_weights)
         self._quant_scratch: Optional[torch.Tensor] = None
+        # "fp8": a MoE model's experts_gate_up / experts_down are ops.Fp8ExpertWeight (quantize_experts)
+        self.expert_quant: Optional[str] = None
         # MoE models (tests): hook(global layer, positions, ids [T, k], weights [T, k]) -> ids to
         # force, or None to keep the router's choice.  Eager steps only: it reads the routing
         self.route_hook = None
@@ -258,6 +261,7 @@ class LlamaModel:
             return
         if self.weight_quant:
             raise RuntimeError("fold_norms: the weights are quantised; fold before quantize_weights")
+        self._check_not_quantised("fold_norms")
         with torch.no_grad():
             for L in self.layers:
                 for w, g in ((L.qkv, L.in_norm), (L.gate_up, L.post_norm)):
@@ -289,7 +293,8 @@ class LlamaModel:
         if act_quant not in (None, "fp8"):
             raise ValueError(f"quantize_weights: unsupported act_quant {act_quant!r} (supported: None, 'fp8')")
         if self.cfg.is_moe:
-            raise ValueError(f"quantize_weights: {self.cfg.name} is a MoE model; quantised experts are not supported")
+            raise ValueError(f"quantize_weights: {self.cfg.name} is a MoE model; its projections stay bf16, and its "
+                             "experts are quantised by quantize_experts (EngineConfig.expert_quant)")
         if act_quant and mode != "fp8":
             raise ValueError(f"quantize_weights: act_quant={act_quant!r} needs mode='fp8' (the e4m3 GEMM reads "
                              f"e4m3 weights), not {mode!r}")
@@ -330,10 +335,40 @@ class LlamaModel:
                     getattr(L, k).act = act_quant
         self.act_quant = act_quant
 
+    def quantize_experts(self, mode: str = "fp8") -> "LlamaModel":
+        """FP8 weight-only experts of a MoE model: each layer's ``experts_gate_up`` / ``experts_down``
+        becomes an ``ops.Fp8ExpertWeight`` (``ops.quantize_fp8_experts``: e4m3 codes, one fp32 scale
+        per expert and output channel), layer by layer, dropping the bf16 tensors as it goes.  The
+        attention projections, the router, the norms and the embeddings keep their dtype; steps run
+        the same ``ops.moe_mlp``, whose two GEMMs become ``moe_gemm_w8``.  Idempotent."""
+        if mode == "mxfp4":
+            raise ValueError("quantize_experts: 'mxfp4' is not supported for experts yet (supported: 'fp8')")
+        if mode != "fp8":
+            raise ValueError(f"quantize_experts: unsupported mode {mode!r} (supported: 'fp8')")
+        if not self.cfg.is_moe:
+            raise ValueError(f"quantize_experts: {self.cfg.name} is a dense model; quantise its projections with "
+                             "quantize_weights (EngineConfig.weight_quant)")
+        if self.expert_quant == mode:
+            return self
+        for L in self.layers:
+            for k in EXPERT_SLOTS:
+                w = getattr(L, k)
+                if not isinstance(w, ops.Fp8ExpertWeight):
+                    setattr(L, k, ops.quantize_fp8_experts(w))
+                    del w
+        self.expert_quant = mode
+        if self.device.type == "cuda":
+            # the KV budget reads driver-free memory: hand the freed bf16 blocks back to the driver
+            torch.cuda.empty_cache()
+        return self
+
     def _check_not_quantised(self, what: str) -> None:
         if self.weight_quant:
             raise RuntimeError(f"{what}: the model's weights are {self.weight_quant}-quantised; "
                                "load or copy the bf16 weights first, then call quantize_weights")
+        if self.expert_quant:
+            raise RuntimeError(f"{what}: the model's experts are {self.expert_quant}-quantised; "
+                               "load or copy the bf16 weights first, then call quantize_experts")
 
     def load_state_dict_hf(self, sd: dict):
         """Load HF Llama tensor names (``model.layers.N.self_attn.q_proj.weight``...)."""
@@ -398,7 +433,7 @@ class LlamaModel:
         for i, L in enumerate(self.layers):
             for k in LlamaLayerWeights.__slots__:
                 t = getattr(L, k)
-                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight)):
+                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
                     yield f"layers.{self.layer_start + i}.{k}.q", t.q
                     yield f"layers.{self.layer_start + i}.{k}.scale", t.scale
                 elif t is not None:
@@ -419,6 +454,9 @@ class LlamaModel:
         if self.act_quant != other.act_quant:
             raise RuntimeError(f"copy_from: this model's act_quant is {self.act_quant!r}, the source's "
                                f"{other.act_quant!r}; quantize_weights both with the same act_quant")
+        if self.expert_quant != other.expert_quant:
+            raise RuntimeError(f"copy_from: this model's experts are {self.expert_quant or 'unquantised'}, the "
+                               f"source's {other.expert_quant or 'unquantised'}; copy first, then quantize_experts")
         src = dict(other.tensors())
         self.norms_folded = other.norms_folded
         for name, t in self.tensors():
@@ -431,7 +469,7 @@ class LlamaModel:
         for L in self.layers:
             for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias, L.q_norm, L.k_norm,
                       L.router, L.experts_gate_up, L.experts_down):
-                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight)):
+                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
                     n += t.nbytes()      # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements)
                 elif t is not None:
                     n += t.numel() * t.element_size()

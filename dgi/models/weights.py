@@ -136,6 +136,8 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
 
     ``model.cfg`` is the LOCAL config (per-rank heads / intermediate for TP);
     ``full`` is the checkpoint's.  Returns {"tensors": n, "bytes": b}."""
+    if hasattr(model, "_check_not_quantised"):     # the loader writes the bf16 tensors in place
+        model._check_not_quantised("load_checkpoint")
     model.norms_folded = False
     rd = CheckpointReader(path)
     c = model.cfg

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from dgi.ops.fp8 import E4M3_MAX, Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
+from dgi.ops.fp8 import Fp8ExpertWeight, quantize_fp8_experts  # noqa: F401  (public: the MoE experts' container)
 from dgi.ops.mxfp4 import Mxfp4Weight, quantize_mxfp4  # noqa: F401  (public: ops.Mxfp4Weight, ops.quantize_mxfp4)
 
 _LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_C.so")
@@ -1330,10 +1331,26 @@ def _silu_mul_f32(gu: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.silu(gu[..., :I]) * gu[..., I:]
 
 
-def moe_gemm_ref(x: torch.Tensor, w: torch.Tensor, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
+def _expert_f32(w, e: int) -> torch.Tensor:
+    """Expert ``e`` of ``w`` ([E, N, K] tensor or ``Fp8ExpertWeight``) in fp32; the container is
+    dequantised as ``linear_fp8_ref`` does (``q.float() * scale[:, None]``)."""
+    return w[e].dequant(torch.float32) if isinstance(w, Fp8ExpertWeight) else w[e].float()
+
+
+def _expert_pair_quantised(gate_up, down) -> bool:
+    """Whether the block's experts are ``Fp8ExpertWeight``: both, or neither."""
+    qg, qd = isinstance(gate_up, Fp8ExpertWeight), isinstance(down, Fp8ExpertWeight)
+    if qg != qd:
+        raise ValueError("moe_mlp: gate_up and down must both be Fp8ExpertWeight or both be tensors, got "
+                         f"{type(gate_up).__name__} and {type(down).__name__}")
+    return qg
+
+
+def moe_gemm_ref(x: torch.Tensor, w, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
                  epi: int, BM: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The definition of ``moe_gemm``: row p of row block b is ``A[p] · w[block_expert[b]]^T`` with
-    fp32 accumulation, rounded once to ``x.dtype``.  SwiGLU (``epi`` 1, ``w = [gate; up]``): A[p] is
+    fp32 accumulation, rounded once to ``x.dtype``; an ``Fp8ExpertWeight`` is dequantised per expert
+    (``q.float() * scale[:, None]``).  SwiGLU (``epi`` 1, ``w = [gate; up]``): A[p] is
     token ``sorted_slot[p] // k`` of ``x`` and the fp32 ``silu(gate) * up`` is what is rounded; plain:
     A[p] is row p of ``x``.  Padding rows (slot -1) are left as ``out`` had them (zeros without ``out``)."""
     P = sorted_slot.numel()
@@ -1345,7 +1362,7 @@ def moe_gemm_ref(x: torch.Tensor, w: torch.Tensor, sorted_slot: torch.Tensor, bl
     for e in torch.unique(row_e[slot >= 0]).tolist():
         rows = torch.nonzero((row_e == e) & (slot >= 0)).flatten()
         a = x[slot[rows] // k] if epi else x[rows]
-        y = a.float() @ w[e].float().t()
+        y = a.float() @ _expert_f32(w, e).t()
         out[rows] = (_silu_mul_f32(y) if epi else y).to(out.dtype)
     return out
 
@@ -1357,12 +1374,32 @@ def _moe_gemm_native(x: torch.Tensor, w: torch.Tensor, epi: int) -> bool:
             and N % 16 == 0 and w.shape[0] <= MOE_MAX_EXPERTS and x.data_ptr() % 16 == 0)
 
 
-def moe_gemm(x: torch.Tensor, w: torch.Tensor, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
+def _moe_gemm_w8_native(x: torch.Tensor, w: Fp8ExpertWeight, epi: int) -> bool:
+    N = w.shape[1] // 2 if epi else w.shape[1]
+    return (x.is_cuda and w.q.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1
+            and x.stride(0) % 8 == 0 and x.shape[1] % 256 == 0 and x.shape[1] == w.shape[2] and N % 16 == 0
+            and w.shape[0] <= MOE_MAX_EXPERTS and x.data_ptr() % 16 == 0 and w.q.data_ptr() % 16 == 0
+            and w.scale.data_ptr() % 16 == 0)
+
+
+def moe_gemm(x: torch.Tensor, w, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
              epi: int, BM: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Grouped GEMM over the sorted layout (``moe_align``): ``[P, N]`` in sorted order.  ``epi``
     ``MOE_EPI_SWIGLU`` gathers token rows of ``x [T, K]`` and applies SwiGLU over ``w [E, 2N, K]``;
     ``MOE_EPI_PLAIN`` reads ``x [P, K]`` in sorted order against ``w [E, N, K]``.  ``k`` is the experts
-    per token (the slot -> token divisor).  The HIP kernel takes bf16, K % 256 == 0, N % 16 == 0."""
+    per token (the slot -> token divisor).  The HIP kernel takes bf16, K % 256 == 0, N % 16 == 0.
+    ``w`` may be an ``Fp8ExpertWeight`` (``moe_gemm_w8``: e4m3 codes, per-expert per-channel scales)."""
+    if isinstance(w, Fp8ExpertWeight):
+        if not _moe_gemm_w8_native(x, w, epi):
+            return moe_gemm_ref(x, w, sorted_slot, block_expert, k, epi, BM, out)
+        load_native(required=True)
+        P = sorted_slot.numel()
+        N = w.shape[1] // 2 if epi else w.shape[1]
+        if out is None:
+            out = torch.empty(P, N, dtype=x.dtype, device=x.device)
+        nslots = x.shape[0] * k if epi else P
+        _call("moe_gemm_w8", out, x, w.q, w.scale, sorted_slot, block_expert, k, nslots, epi, BM)
+        return out
     if _moe_gemm_native(x, w, epi):
         load_native(required=True)
         P = sorted_slot.numel()
@@ -1400,12 +1437,14 @@ def moe_combine(y: torch.Tensor, inv: torch.Tensor, weights: torch.Tensor) -> to
     return moe_combine_ref(y, inv, weights)
 
 
-def moe_mlp_ref(x: torch.Tensor, router_w: torch.Tensor, gate_up: torch.Tensor, down: torch.Tensor, k: int,
-                norm_topk: bool, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+def moe_mlp_ref(x: torch.Tensor, router_w: torch.Tensor, gate_up, down, k: int, norm_topk: bool,
+                ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The definition of ``moe_mlp``, as the per-expert loop: router logits ``x @ router_w^T`` in
     ``x.dtype``, ``moe_route_ref`` (or the forced ``ids`` with the model's own probabilities at them),
     then for every expert its tokens through ``silu(gate) * up`` (fp32, rounded to ``x.dtype``) and
-    ``down`` (fp32 accumulate, rounded), combined by ``moe_combine_ref``."""
+    ``down`` (fp32 accumulate, rounded), combined by ``moe_combine_ref``.  ``gate_up`` and ``down``
+    may both be ``Fp8ExpertWeight``: each expert is then dequantised to fp32 first."""
+    _expert_pair_quantised(gate_up, down)
     T, H = x.shape
     logits = torch.nn.functional.linear(x, router_w)
     if ids is None:
@@ -1418,29 +1457,36 @@ def moe_mlp_ref(x: torch.Tensor, router_w: torch.Tensor, gate_up: torch.Tensor, 
     for e in torch.unique(flat).tolist():
         slots = torch.nonzero(flat == e).flatten()
         a = x[slots // k].float()
-        act = _silu_mul_f32(a @ gate_up[e].float().t()).to(x.dtype)
-        y[slots] = (act.float() @ down[e].float().t()).to(x.dtype)
+        act = _silu_mul_f32(a @ _expert_f32(gate_up, e).t()).to(x.dtype)
+        y[slots] = (act.float() @ _expert_f32(down, e).t()).to(x.dtype)
     inv = torch.arange(T * k, dtype=torch.int32, device=x.device)
     return moe_combine_ref(y, inv, weights)
 
 
-def moe_mlp_ok(x: torch.Tensor, router_w: torch.Tensor, gate_up: torch.Tensor, down: torch.Tensor, k: int) -> bool:
+def moe_mlp_ok(x: torch.Tensor, router_w: torch.Tensor, gate_up, down, k: int) -> bool:
     """Whether the HIP kernels take this MoE block (else ``moe_mlp`` is ``moe_mlp_ref``)."""
     E, I2, H = gate_up.shape
+    if _expert_pair_quantised(gate_up, down):
+        return (x.is_cuda and x.dim() == 2 and x.shape[0] > 0 and x.dtype == torch.bfloat16
+                and gate_up.q.is_cuda and down.q.is_cuda and H % 256 == 0 and (I2 // 2) % 256 == 0
+                and gate_up.q.data_ptr() % 16 == 0 and gate_up.scale.data_ptr() % 16 == 0
+                and down.q.data_ptr() % 16 == 0 and down.scale.data_ptr() % 16 == 0
+                and E <= MOE_MAX_EXPERTS and 1 <= k <= min(E, MOE_MAX_TOPK) and x.shape[0] * k < (1 << 30))
     return (x.is_cuda and x.dim() == 2 and x.shape[0] > 0 and x.dtype == torch.bfloat16
             and gate_up.dtype == torch.bfloat16 and down.dtype == torch.bfloat16
             and gate_up.is_contiguous() and down.is_contiguous() and H % 256 == 0 and (I2 // 2) % 256 == 0
             and E <= MOE_MAX_EXPERTS and 1 <= k <= min(E, MOE_MAX_TOPK) and x.shape[0] * k < (1 << 30))
 
 
-def moe_mlp(x: torch.Tensor, router_w: torch.Tensor, gate_up: torch.Tensor, down: torch.Tensor, k: int,
-            norm_topk: bool, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+def moe_mlp(x: torch.Tensor, router_w: torch.Tensor, gate_up, down, k: int, norm_topk: bool,
+            ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Top-k routed SwiGLU experts (no shared expert): ``x [T, H]``, ``router_w [E, H]``,
     ``gate_up [E, 2I, H]`` (``[gate; up]`` per expert), ``down [E, H, I]`` -> ``[T, H]``.  On the
     GPU: the router through ``linear``, then ``moe_route`` -> ``moe_align`` -> ``moe_gemm`` (SwiGLU)
     -> ``moe_gemm`` (plain) -> ``moe_combine``; nothing is read back, so the block captures into a
     graph.  ``ids`` forces the routing (tests): the weights are then the model's own softmax
-    probabilities at those ids."""
+    probabilities at those ids.  FP8 weight-only experts: ``gate_up`` and ``down`` both as
+    ``Fp8ExpertWeight`` (a mix raises); the two GEMMs are then ``moe_gemm_w8``, nothing else changes."""
     if not moe_mlp_ok(x, router_w, gate_up, down, k):
         return moe_mlp_ref(x, router_w, gate_up, down, k, norm_topk, ids)
     T = x.shape[0]

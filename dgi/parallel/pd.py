@@ -57,7 +57,7 @@ import numpy as np
 import torch
 
 from dgi import ops
-from dgi.engine import EngineConfig, LLMEngine, StepOutput, refuse_fp8_kv
+from dgi.engine import EngineConfig, LLMEngine, StepOutput, refuse_expert_quant, refuse_fp8_kv
 from dgi.models.config import get_config
 from dgi.parallel.fabric import CtrlChannel, Fabric
 from dgi.parallel.kv_transfer import KVReceiver, KVSender, scatter_groups
@@ -137,6 +137,7 @@ class PrefillServer:
                  local_cap: int = 0, report_tokens: bool = False, router: Optional[int] = None,
                  stream_layers: int = 8):
         refuse_fp8_kv(cfg, "prefill/decode disaggregation")
+        refuse_expert_quant(cfg, "prefill/decode disaggregation")
         self.f = fabric
         self.layout = layout
         self.drivers = list(layout.drivers)
@@ -492,6 +493,7 @@ class DecodeDriver:
     def __init__(self, cfg: EngineConfig, fabric: Fabric, layout: NodeLayout, credit_margin: float = 0.02,
                  local_fraction: float = 0.0, router: Optional[int] = None):
         refuse_fp8_kv(cfg, "prefill/decode disaggregation")
+        refuse_expert_quant(cfg, "prefill/decode disaggregation")
         self.f = fabric
         self.layout = layout
         self.group = layout.group_of(fabric.rank)

@@ -44,7 +44,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from dgi.engine import EngineConfig, LLMEngine, StepOutput, refuse_fp8_kv
+from dgi.engine import EngineConfig, LLMEngine, StepOutput, refuse_expert_quant, refuse_fp8_kv
 from dgi.models.config import ModelConfig, get_config
 from dgi.models.llama import LlamaModel
 from dgi.kv.block_pool import BlockPool, OutOfBlocks, num_blocks_for_budget
@@ -264,6 +264,7 @@ class PipelineEngine(LLMEngine):
                  kv_sources: Optional[list] = None):
         from dgi.parallel.fabric import CtrlChannel
         refuse_fp8_kv(cfg, "the layer pipeline")
+        refuse_expert_quant(cfg, "the layer pipeline")
         self.f = fabric
         self.ranks = list(stage_ranks)
         assert self.ranks[0] == fabric.rank
@@ -517,6 +518,7 @@ class StageWorker:
                  kv_sources: Optional[list] = None):
         from dgi.parallel.fabric import CtrlChannel
         refuse_fp8_kv(cfg, "the layer pipeline")
+        refuse_expert_quant(cfg, "the layer pipeline")
         self.f = fabric
         self.mb_cap = max(1, cfg.max_num_seqs // (microbatches or len(stage_ranks)))
         self.ranks = list(stage_ranks)

@@ -27,7 +27,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from dgi.engine import EngineConfig, LLMEngine, engine_block_budget, refuse_fp8_kv
+from dgi.engine import EngineConfig, LLMEngine, engine_block_budget, refuse_expert_quant, refuse_fp8_kv
 from dgi.models.config import ModelConfig, get_config
 from dgi.models.llama import LlamaLayerWeights, LlamaModel, _rand
 
@@ -110,6 +110,7 @@ class TPEngine(LLMEngine):
         from dgi.models.weights import resolve_checkpoint
         if tp > 1:
             refuse_fp8_kv(cfg, "tensor parallel")
+            refuse_expert_quant(cfg, "tensor parallel")
         ckpt = resolve_checkpoint(cfg.model, cfg.model_path)
         full = model_cfg or get_config(ckpt or cfg.model)
         full.max_position = max(full.max_position, cfg.max_model_len)

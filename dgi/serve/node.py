@@ -101,7 +101,8 @@ class Router:
         cfg = EngineConfig(model=args.model, device=dev, max_num_seqs=args.max_num_seqs,
                            max_num_batched_tokens=args.max_batched_tokens, max_model_len=args.max_model_len,
                            use_graphs=dev.startswith("cuda") and not args.no_graphs, seed=args.seed,
-                           weight_quant=args.weight_quant, act_quant=args.act_quant, kv_dtype=args.kv_dtype)
+                           weight_quant=args.weight_quant, act_quant=args.act_quant, kv_dtype=args.kv_dtype,
+                           expert_quant=getattr(args, "expert_quant", None))
         self.drv = None
         self.chans = {}
         self.load = collections.Counter()
@@ -409,8 +410,14 @@ def main(argv=None) -> int:
     ap.add_argument("--kv-dtype", default=None, choices=["fp8"],
                     help="KV cache pages as e4m3 codes with per-head scales (default: bf16 pages); "
                          "single-GPU engines only")
+    ap.add_argument("--expert-quant", default=None, choices=["fp8"],
+                    help="MoE models: FP8 weight-only experts (e4m3 codes, per-expert per-channel scales); the "
+                         "attention projections stay bf16 (default: bf16 experts); single-GPU engine only")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.expert_quant and world > 1:
+        ap.error("--expert-quant is supported by the single-GPU engine only (as MoE models are): run one rank, "
+                 "or leave it unset")
     fabric = layout = None
     if world > 1:
         from dgi.parallel.fabric import Fabric

@@ -30,14 +30,16 @@ def main():
     ap.add_argument("--prefill-tokens", type=int, default=0,
                     help="also time one prefill step of this many tokens (one prompt, after the decode batches)")
     ap.add_argument("--kv-dtype", default=None, choices=["fp8"], help="fp8 (e4m3) KV cache pages")
+    ap.add_argument("--expert-quant", default=None, choices=["fp8"], help="MoE models: FP8 weight-only experts")
     ap.add_argument("--num-blocks", type=int, default=None, help="KV pages (default: from free memory)")
     a = ap.parse_args()
     cfg = EngineConfig(model=a.model, device="cuda", max_num_seqs=max(a.batch), max_num_batched_tokens=8192,
                        max_model_len=max(2048, a.prefill_tokens + 64), kv_fraction=0.5, weight_quant=a.weight_quant,
                        act_quant=a.act_quant,
-                       kv_dtype=a.kv_dtype, num_blocks=a.num_blocks)
+                       kv_dtype=a.kv_dtype, num_blocks=a.num_blocks, expert_quant=a.expert_quant)
     eng = LLMEngine(cfg)
-    print(json.dumps({"model": a.model, "weight_quant": a.weight_quant, "act_quant": a.act_quant, "kv_dtype": a.kv_dtype, "weight_bytes": eng.model.weight_bytes(),
+    print(json.dumps({"model": a.model, "weight_quant": a.weight_quant, "act_quant": a.act_quant, "kv_dtype": a.kv_dtype,
+                      "expert_quant": a.expert_quant, "weight_bytes": eng.model.weight_bytes(),
                       "num_blocks": eng.pool.num_blocks}), flush=True)
     eng.warmup()
     g = torch.Generator().manual_seed(0)
@@ -63,7 +65,7 @@ def main():
         while eng.has_unfinished():
             eng.step()
         rows.append({"model": a.model, "batch": B, "tpot_ms": round(ms, 3), "tok_s": round(B / ms * 1000, 1), "weight_quant": a.weight_quant,
-                     "act_quant": a.act_quant, "kv_dtype": a.kv_dtype,
+                     "act_quant": a.act_quant, "kv_dtype": a.kv_dtype, "expert_quant": a.expert_quant,
                      "skinny_max_m": int(os.environ.get("DGI_SKINNY_MAX_M", "32")), "host_phases_ms": ph})
         print(json.dumps(rows[-1]), flush=True)
     if a.prefill_tokens > 0:

@@ -58,6 +58,9 @@ def main():
     ap.add_argument("--layers", type=int, default=6, help="independent weight copies a replay walks")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None, help="write the JSON rows here as well")
+    ap.add_argument("--expert-quant", default=None, choices=["fp8"],
+                    help="also time the block and both grouped GEMMs over FP8 weight-only experts "
+                         "(ops.quantize_fp8_experts of the same weights), beside the bf16 ones")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moe_bench: needs a GPU")
@@ -70,6 +73,11 @@ def main():
     gate_up = [(rn(E, 2 * I, H) / H ** 0.5).bfloat16() for _ in range(L)]
     down = [(rn(E, H, I) / I ** 0.5).bfloat16() for _ in range(L)]
     expert_bytes = 3 * H * I * 2
+    gate_up_q = down_q = None
+    if a.expert_quant == "fp8":
+        gate_up_q = [ops.quantize_fp8_experts(w) for w in gate_up]
+        down_q = [ops.quantize_fp8_experts(w) for w in down]
+        expert_bytes_q = 3 * H * I + 4 * (2 * I + H)      # codes + one fp32 scale per output channel
     rows = []
     for T in a.tokens:
         x = [rn(T, H).bfloat16() for _ in range(L)]
@@ -90,6 +98,16 @@ def main():
                                                              ops.MOE_EPI_PLAIN, BM), L, a.reps),
              "combine_ms": graph_ms(lambda l: ops.moe_combine(y[l], lay[l][4], routed[l][1]), L, a.reps),
              "moe_mlp_ms": graph_ms(lambda l: ops.moe_mlp(x[l], router[l], gate_up[l], down[l], k, True), L, a.reps)}
+        if gate_up_q is not None:
+            act_q = [ops.moe_gemm(x[l], gate_up_q[l], lay[l][2], lay[l][3], k, ops.MOE_EPI_SWIGLU, BM) for l in range(L)]
+            r["fp8_gemm_swiglu_ms"] = graph_ms(lambda l: ops.moe_gemm(x[l], gate_up_q[l], lay[l][2], lay[l][3], k,
+                                                                      ops.MOE_EPI_SWIGLU, BM), L, a.reps)
+            r["fp8_gemm_down_ms"] = graph_ms(lambda l: ops.moe_gemm(act_q[l], down_q[l], lay[l][2], lay[l][3], k,
+                                                                    ops.MOE_EPI_PLAIN, BM), L, a.reps)
+            r["fp8_moe_mlp_ms"] = graph_ms(lambda l: ops.moe_mlp(x[l], router[l], gate_up_q[l], down_q[l], k, True),
+                                           L, a.reps)
+            r["fp8_expert_GBps"] = distinct * expert_bytes_q / (
+                (r["fp8_gemm_swiglu_ms"] + r["fp8_gemm_down_ms"]) * 1e-3) / 1e9
         # the per-expert torch loop: host read-back per layer, so a host clock around a synchronise
         for _ in range(2):
             ops.moe_mlp_ref(x[0], router[0], gate_up[0], down[0], k, True)
@@ -116,6 +134,8 @@ def main():
         print(json.dumps(rows[-1]), flush=True)
     cols = ["T", "BM", "distinct_experts", "moe_mlp_ms", "torch_loop_ms", "router_linear_ms", "route_ms", "align_ms",
             "gemm_swiglu_ms", "gemm_down_ms", "combine_ms", "expert_GBps", "skinny_GBps"]
+    if gate_up_q is not None:
+        cols += ["fp8_moe_mlp_ms", "fp8_gemm_swiglu_ms", "fp8_gemm_down_ms", "fp8_expert_GBps"]
     print("| " + " | ".join(cols) + " |")
     print("|" + "---|" * len(cols))
     for r in rows:
@@ -123,7 +143,8 @@ def main():
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
-            json.dump({"hidden": H, "inter": I, "experts": E, "topk": k, "layers": L, "rows": rows}, f, indent=1)
+            json.dump({"hidden": H, "inter": I, "experts": E, "topk": k, "layers": L,
+                       "expert_quant": a.expert_quant, "rows": rows}, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,8 @@ Config keys accepted (SURVEY Appendix C mapping): ``model_id``, ``device``,
 ``num_blocks``, ``use_graphs``/``enforce_eager``, ``quantization``/``weight_quant``
 (``"fp8"``: weight-only e4m3 projections, ``"mxfp4"``: weight-only OCP MXFP4 projections; anything else is served
 unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
-``DGI_W8A8_MIN_M`` rows, default 2048; ``quantization: "fp8"`` alone stays W8A16); nested ``sglang``/``vllm``/
+``DGI_W8A8_MIN_M`` rows, default 2048; ``quantization: "fp8"`` alone stays W8A16), ``expert_quant`` (``"fp8"``:
+weight-only e4m3 experts of a MoE model; anything else, or a dense model, is served with bf16 experts); nested ``sglang``/``vllm``/
 ``native`` dicts are merged in.
 """
 from __future__ import annotations
@@ -115,6 +116,14 @@ class NativeLLMEngine(LLMBaseEngine):
             logger.warning("act_quant=%r is not supported by the native engine (supported: 'fp8', together with "
                            "quantization 'fp8'); serving %s with bf16 activations", actq, model_id)
             actq = None
+        # FP8 weight-only experts are opt-in, and a MoE model's knob only
+        expq = c.get("expert_quant")
+        if expq is not None and str(expq).lower() in ("", "none"):
+            expq = None
+        if expq is not None and (str(expq).lower() != "fp8" or not mc.is_moe):
+            logger.warning("expert_quant=%r is not supported by the native engine (supported: 'fp8', for a MoE "
+                           "model); serving %s with bf16 experts", expq, model_id)
+            expq = None
         # vLLM / SGLang name it kv_cache_dtype; "auto" and the activation dtypes mean no KV quantisation
         kvd = c.get("kv_cache_dtype", c.get("kv_dtype"))
         if kvd is not None and str(kvd).lower() in ("", "none", "auto", "bf16", "bfloat16"):
@@ -136,6 +145,7 @@ class NativeLLMEngine(LLMBaseEngine):
             host_kv_gb=float(c.get("host_kv_gb", 0.0)), weight_quant=quant,
             act_quant="fp8" if actq is not None else None,
             kv_dtype="fp8" if kvd is not None else None,
+            expert_quant="fp8" if expq is not None else None,
             graph_buckets=tuple(c["graph_batch_buckets"]) if c.get("graph_batch_buckets") else None)
         spec = c.get("speculative")
         if spec:

@@ -4,6 +4,7 @@
 // whole decode step can be captured into a hipGraph (torch.cuda.CUDAGraph on
 // ROCm).  Shapes are checked here, on the host, before any launch: a kernel
 // never sees operands that disagree with its grid.
+#include <climits>
 #include <cstdlib>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -25,13 +26,13 @@ int dgi_paged_decode(const void* q, int q_stride, const void* k_cache, const voi
                      const int* block_tables, int bt_stride, const int* context_lens, void* out,
                      int out_stride, float* part_o, float* part_lse, int* counters, int B, int nh, int nkv,
                      int hd, int block_size, int max_splits, int part_size, float scale, const float* kv_scale,
-                     hipStream_t s);
+                     int window, hipStream_t s);
 int dgi_paged_prefill(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                       const int* block_tables, int bt_stride, const int* cu_seqlens_q,
                       const int* context_lens, const int* tiles, int n_tiles, void* out,
                       int out_stride, int nh, int nkv, int hd, int block_size, float scale,
                       const unsigned long long* tree_mask, int tree_n, int tile_rows, const float* kv_scale,
-                      hipStream_t s);
+                      int window, hipStream_t s);
 int dgi_silu_mul(const void* gu, void* out, int T, int I, hipStream_t s);
 int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int M,
                     int N, int K, int nw, hipStream_t s);
@@ -230,8 +231,10 @@ void paged_decode(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cache
                   const at::Tensor& v_cache, const at::Tensor& block_tables,
                   const at::Tensor& context_lens, at::Tensor part_o, at::Tensor part_lse,
                   int64_t nh, int64_t nkv, int64_t max_splits, int64_t part_size, double scale,
-                  const c10::optional<at::Tensor>& counters, const c10::optional<at::Tensor>& kv_scale) {
+                  const c10::optional<at::Tensor>& counters, const c10::optional<at::Tensor>& kv_scale,
+                  int64_t window) {
   check_bf16(out, "out"); check_bf16(q, "q");
+  TORCH_CHECK(window >= 0 && window <= INT_MAX, "paged_decode: window must be >= 0 (0 = none), got ", window);
   const float* ksc = check_kv(k_cache, v_cache, kv_scale, nkv, "paged_decode");
   check_i32_rows(block_tables, "block_tables"); check_i32(context_lens, "context_lens");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1 && out.dim() == 2 && out.stride(1) == 1);
@@ -257,7 +260,7 @@ void paged_decode(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cache
                             max_splits > 1 ? part_o.data_ptr<float>() : nullptr,
                             max_splits > 1 ? part_lse.data_ptr<float>() : nullptr, cnt, B, (int)nh,
                             (int)nkv, hd, (int)k_cache.size(2), (int)max_splits, (int)part_size,
-                            (float)scale, ksc, cur_stream()),
+                            (float)scale, ksc, (int)window, cur_stream()),
            "paged_decode");
 }
 
@@ -266,8 +269,9 @@ void paged_prefill(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cach
                    const at::Tensor& cu_seqlens_q, const at::Tensor& context_lens,
                    const at::Tensor& tiles, int64_t nh, int64_t nkv, double scale,
                    const c10::optional<at::Tensor>& tree_mask, int64_t tree_n, int64_t tile_rows,
-                   const c10::optional<at::Tensor>& kv_scale) {
+                   const c10::optional<at::Tensor>& kv_scale, int64_t window) {
   check_bf16(out, "out"); check_bf16(q, "q");
+  TORCH_CHECK(window >= 0 && window <= INT_MAX, "paged_prefill: window must be >= 0 (0 = none), got ", window);
   const float* ksc = check_kv(k_cache, v_cache, kv_scale, nkv, "paged_prefill");
   check_i32_rows(block_tables, "block_tables"); check_i32(cu_seqlens_q, "cu_seqlens_q");
   check_i32(context_lens, "context_lens"); check_i32(tiles, "tiles");
@@ -282,12 +286,15 @@ void paged_prefill(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cach
     TORCH_CHECK(tree_mask->size(-1) == 64 && tree_mask->numel() >= 64 * (cu_seqlens_q.numel() - 1));
     tm = reinterpret_cast<const unsigned long long*>(tree_mask->data_ptr<int64_t>());
   }
+  TORCH_CHECK(!(window > 0 && tm != nullptr && tree_n > 0),
+              "paged_prefill: a sliding window cannot be combined with a tree mask (tree positions are not "
+              "row indices)");
   check_rc(dgi_paged_prefill(q.data_ptr(), (int)q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
                              block_tables.data_ptr<int>(), (int)block_tables.stride(0),
                              cu_seqlens_q.data_ptr<int>(), context_lens.data_ptr<int>(),
                              tiles.data_ptr<int>(), (int)tiles.size(0), out.data_ptr(),
                              (int)out.stride(0), (int)nh, (int)nkv, hd, (int)k_cache.size(2),
-                             (float)scale, tm, (int)tree_n, (int)tile_rows, ksc, cur_stream()),
+                             (float)scale, tm, (int)tree_n, (int)tile_rows, ksc, (int)window, cur_stream()),
            "paged_prefill");
 }
 
@@ -953,10 +960,10 @@ TORCH_LIBRARY(dgi, m) {
         "Tensor? kv_inv_scale=None) -> ()");
   m.def("paged_decode(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor context_lens, Tensor(b!) part_o, Tensor(c!) part_lse, int nh, int nkv, int max_splits, "
-        "int part_size, float scale, Tensor(d!)? counters=None, Tensor? kv_scale=None) -> ()");
+        "int part_size, float scale, Tensor(d!)? counters=None, Tensor? kv_scale=None, int window=0) -> ()");
   m.def("paged_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor cu_seqlens_q, Tensor context_lens, Tensor tiles, int nh, int nkv, float scale, "
-        "Tensor? tree_mask, int tree_n, int tile_rows=128, Tensor? kv_scale=None) -> ()");
+        "Tensor? tree_mask, int tree_n, int tile_rows=128, Tensor? kv_scale=None, int window=0) -> ()");
   m.def("silu_mul(Tensor(a!) out, Tensor gu) -> ()");
   m.def("moe_route(Tensor(a!) ids, Tensor(b!) weights, Tensor logits, int k, bool norm) -> ()");
   m.def("moe_align(Tensor(a!) counts, Tensor(b!) offsets, Tensor(c!) sorted_slot, Tensor(d!) block_expert, "

@@ -125,6 +125,12 @@ __device__ __forceinline__ uint2 quant8_e4m3(const float* x, float inv_scale) {
 // The optional trailing kernel argument of the fp8-KV instantiations (a parameter pack that is
 // empty for bf16, so the bf16 kernels keep their argument list).
 __device__ __forceinline__ const float* pack_ptr(const float* p) { return p; }
+// The sliding-window instantiations of the attention kernels put their window (tokens, > 0) in
+// front of it, so the pack is (), (kv_scale), (window) or (window, kv_scale) and the unwindowed
+// kernels keep their argument lists too.
+__device__ __forceinline__ const float* pack_ptr(int, const float* p) { return p; }
+__device__ __forceinline__ int pack_window(int w) { return w; }
+__device__ __forceinline__ int pack_window(int w, const float*) { return w; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

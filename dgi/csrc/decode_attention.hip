@@ -25,6 +25,12 @@
 //   in the same launch (ticket counters in the workspace: write-through
 //   partials, one relaxed ticket, one acquire on the last arriver) or a small
 //   reduce kernel does.
+//   Sliding window (WIN instantiations, window W > 0): the row sees keys [lo, ctx) with
+//   lo = max(0, ctx - W).  The split plan is made over [base, ctx), base = lo & ~31 (tile
+//   bases stay 32-aligned for the 16-token-page path), and only the first tile of split 0
+//   has tokens below lo to mask.  base <= lo < ctx and parts of >= 32 tokens put lo into that
+//   first tile, so no tile is wholly masked (the running max relies on it) and no K/V slot
+//   below base is read.  window == 0 launches the WIN = false instantiations: today's code.
 #include <type_traits>
 
 #include "common.h"
@@ -55,19 +61,44 @@ constexpr int decode_wave_lds() {
   return (32 * HD * 2 > 16 * (HD + 4) * 4 ? 32 * HD * 2 : 16 * (HD + 4) * 4) + 128;
 }
 
+// The split plan of one sequence, shared by the attention kernel, its fused ticket reduce and
+// decode_reduce_kernel: parts of `part` tokens from `base` (0 without a window).
+// part_size <= 0: device-side split plan from this sequence's own span —
+// up to max_splits parts of at least -part_size tokens (32-token multiples),
+// so a graph captured for the longest context does not leave short ones
+// with idle workgroups or a needless reduce
+struct DecodePlan {
+  int base, nsplit, part;
+};
+template <bool WIN>
+__device__ __forceinline__ DecodePlan decode_plan(int ctx, int window, int part_size, int max_splits) {
+  DecodePlan p;
+  p.base = WIN ? (max(0, ctx - window) & ~31) : 0;
+  const int span = ctx - p.base;
+  if (part_size > 0) {
+    p.part = part_size;
+    p.nsplit = (span + p.part - 1) / p.part;
+  } else {
+    p.nsplit = max(1, min(max_splits, (span + (-part_size) - 1) / (-part_size)));
+    p.part = (((span + p.nsplit - 1) / p.nsplit) + 31) & ~31;
+    p.nsplit = (span + p.part - 1) / p.part;
+  }
+  return p;
+}
+
 // FP8: the caches hold e4m3 codes (one byte per element, same page layout).  Only the load stage
 // differs: a lane fetches the 8 codes of each K fragment / V chunk with one 8-byte load and widens
 // them to bf16 in registers (exact) right before the MFMA / the LDS write, so the LDS image, the
 // transposed reads, the MFMA sequence, the softmax and the split reduce are the bf16 kernel's.
 // The trailing argument is kv_scale [2, nkv] fp32: the workgroup's K scale multiplies the softmax
-// scale and its V scale the final normalisation.
-template <int HD, int NW, bool FP8, typename... S>
+// scale and its V scale the final normalisation.  WIN puts the window in front of it.
+template <int HD, int NW, bool FP8, bool WIN, typename... S>
 __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
     const uint16_t* __restrict__ q, int q_stride, const uint16_t* __restrict__ k_cache,
     const uint16_t* __restrict__ v_cache, const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ context_lens, uint16_t* __restrict__ out, int out_stride,
     float* __restrict__ part_o, float* __restrict__ part_lse, int* __restrict__ counters, int max_splits, int nh,
-    int nkv, int bs_log2, int part_size, float scale_log2, bool page16, S... kv_scale) {
+    int nkv, int bs_log2, int part_size, float scale_log2, bool page16, S... extra) {
   constexpr int KS = HD / 32;   // k-steps of the QK^T product
   constexpr int NC = HD / 16;   // 16-wide dim blocks of the PV product
   constexpr int VCH = HD / 8;   // 16-byte chunks per V row
@@ -86,7 +117,7 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
   const int ctx = context_lens[b];
   [[maybe_unused]] float v_scale = 1.f;
   if constexpr (FP8) {
-    const float* sc = pack_ptr(kv_scale...);
+    const float* sc = pack_ptr(extra...);
     scale_log2 *= sc[h];
     v_scale = sc[nkv + h];
   }
@@ -97,20 +128,12 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
       (void*)part_o, 0, (int)min((size_t)gridDim.z * nh * max_splits * HD * 4, (size_t)0x7fffffff), kRsrcWord3);
   const __amdgpu_buffer_rsrc_t pl_rs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)part_lse, 0, (int)min((size_t)gridDim.z * nh * max_splits * 4, (size_t)0x7fffffff), kRsrcWord3);
-  // part_size <= 0: device-side split plan from this sequence's own context —
-  // up to max_splits parts of at least -part_size tokens (32-token multiples),
-  // so a graph captured for the longest context does not leave short ones
-  // with idle workgroups or a needless reduce
-  int nsplit, part;
-  if (part_size > 0) {
-    part = part_size;
-    nsplit = (ctx + part - 1) / part;
-  } else {
-    nsplit = max(1, min(max_splits, (ctx + (-part_size) - 1) / (-part_size)));
-    part = (((ctx + nsplit - 1) / nsplit) + 31) & ~31;
-    nsplit = (ctx + part - 1) / part;
-  }
-  const int start = split * part;
+  int window = 0;
+  if constexpr (WIN) window = pack_window(extra...);
+  [[maybe_unused]] const int lo = max(0, ctx - window);   // WIN: first visible token
+  const DecodePlan plan = decode_plan<WIN>(ctx, window, part_size, max_splits);
+  const int nsplit = plan.nsplit, part = plan.part;
+  const int start = plan.base + split * part;
   if (start >= ctx) return;
   const int end = min(start + part, ctx);
   const int G = nh / nkv;
@@ -243,8 +266,8 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
       else *reinterpret_cast<u32x4*>(vt + v_lds_off<HD>(row, ch * 8)) = vr[k];
     }
     // ---- online softmax (lane owns query qi; tokens 16u + 4g + i); only the sequence's last
-    // tile has tokens past its end to mask
-    const bool full = tb + 32 <= end;
+    // tile has tokens past its end to mask, and only a window's first tile tokens before lo
+    const bool full = tb + 32 <= end && !(WIN && tb < lo);
     float x[2][4];
     float mx = -1e30f;
     if (full) {
@@ -261,7 +284,8 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int tok = tb + 16 * u + 4 * g + i;
-          const float v = (tok < end) ? sacc[u][i] * scale_log2 : -1e30f;
+          const bool vis = WIN ? (tok < end) & (tok >= lo) : tok < end;
+          const float v = vis ? sacc[u][i] * scale_log2 : -1e30f;
           x[u][i] = v;
           mx = fmaxf(mx, v);
         }
@@ -398,22 +422,17 @@ __global__ __launch_bounds__(64 * NW) void paged_decode_kernel(
   }
 }
 
-template <int HD>
+template <int HD, bool WIN, typename... S>
 __global__ __launch_bounds__(HD) void decode_reduce_kernel(
     const float* __restrict__ part_o, const float* __restrict__ part_lse,
     const int* __restrict__ context_lens, uint16_t* __restrict__ out, int out_stride, int max_splits,
-    int nh, int part_size) {
+    int nh, int part_size, S... extra) {
   const int b = blockIdx.x;
   const int head = blockIdx.y;
   const int ctx = context_lens[b];
-  int nsplit;
-  if (part_size > 0) {
-    nsplit = (ctx + part_size - 1) / part_size;
-  } else {  // same device-side plan as the attention kernel
-    nsplit = max(1, min(max_splits, (ctx + (-part_size) - 1) / (-part_size)));
-    const int part = (((ctx + nsplit - 1) / nsplit) + 31) & ~31;
-    nsplit = (ctx + part - 1) / part;
-  }
+  int window = 0;
+  if constexpr (WIN) window = pack_window(extra...);
+  const int nsplit = decode_plan<WIN>(ctx, window, part_size, max_splits).nsplit;   // the attention kernel's
   if (nsplit <= 1) return;
   const size_t base = ((size_t)b * nh + head) * max_splits;
   float M = -1e30f;
@@ -434,7 +453,8 @@ extern "C" int dgi_paged_decode(const void* q, int q_stride, const void* k_cache
                                 const int* context_lens, void* out, int out_stride, float* part_o,
                                 float* part_lse, int* counters, int B, int nh, int nkv, int hd, int block_size,
                                 int max_splits, int part_size, float scale, const float* kv_scale,
-                                hipStream_t s) {
+                                int window, hipStream_t s) {
+  if (window < 0) return -6;
   if (B == 0) return 0;
   if (nh % nkv || nh / nkv > 16) return -2;
   // fixed parts: multiples of 128 tokens; dynamic (part_size <= 0): minimum part a multiple of 32
@@ -456,28 +476,40 @@ extern "C" int dgi_paged_decode(const void* q, int q_stride, const void* k_cache
   // few workgroups (small batch, one split: every (sequence, kv head) walks its whole
   // context): 8 waves per workgroup halve the serial tile chain of each wave
   const bool wide = max_splits == 1 && B * nkv <= 128;
-  // kv_scale != nullptr: the caches hold e4m3 codes
-#define DGI_DECODE(HDV, NWV)                                                                               \
-  do {                                                                                                     \
-    if (kv_scale)                                                                                          \
-      paged_decode_kernel<HDV, NWV, true, const float*><<<grid, 64 * NWV, NWV * decode_wave_lds<HDV>(), s>>>( \
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
-          bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse, counters, max_splits, nh,  \
-          nkv, bs_log2, part_size, scale_log2, page16, kv_scale);                                           \
-    else                                                                                                   \
-      paged_decode_kernel<HDV, NWV, false><<<grid, 64 * NWV, NWV * decode_wave_lds<HDV>(), s>>>(            \
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
-          bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse, counters, max_splits, nh,  \
-          nkv, bs_log2, part_size, scale_log2, page16);                                                     \
+  // kv_scale != nullptr: the caches hold e4m3 codes; window > 0: the WIN instantiations
+#define DGI_DECODE_ARGS                                                                                  \
+  (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,        \
+      bt_stride, context_lens, (uint16_t*)out, out_stride, part_o, part_lse, counters, max_splits, nh,   \
+      nkv, bs_log2, part_size, scale_log2, page16
+#define DGI_DECODE_CFG(HDV, NWV) <<<grid, 64 * NWV, NWV * decode_wave_lds<HDV>(), s>>>
+#define DGI_DECODE(HDV, NWV)                                                                             \
+  do {                                                                                                   \
+    if (window > 0 && kv_scale)                                                                          \
+      paged_decode_kernel<HDV, NWV, true, true, int, const float*> DGI_DECODE_CFG(HDV, NWV)(             \
+          DGI_DECODE_ARGS, window, kv_scale);                                                            \
+    else if (window > 0)                                                                                 \
+      paged_decode_kernel<HDV, NWV, false, true, int> DGI_DECODE_CFG(HDV, NWV)(DGI_DECODE_ARGS, window); \
+    else if (kv_scale)                                                                                   \
+      paged_decode_kernel<HDV, NWV, true, false, const float*> DGI_DECODE_CFG(HDV, NWV)(DGI_DECODE_ARGS, \
+                                                                                        kv_scale);       \
+    else                                                                                                 \
+      paged_decode_kernel<HDV, NWV, false, false> DGI_DECODE_CFG(HDV, NWV)(DGI_DECODE_ARGS);             \
+  } while (0)
+#define DGI_DECODE_REDUCE(HDV)                                                                           \
+  do {                                                                                                   \
+    if (window > 0)                                                                                      \
+      decode_reduce_kernel<HDV, true, int><<<dim3(B, nh), HDV, 0, s>>>(                                  \
+          part_o, part_lse, context_lens, (uint16_t*)out, out_stride, max_splits, nh, part_size, window); \
+    else                                                                                                 \
+      decode_reduce_kernel<HDV, false><<<dim3(B, nh), HDV, 0, s>>>(                                      \
+          part_o, part_lse, context_lens, (uint16_t*)out, out_stride, max_splits, nh, part_size);        \
   } while (0)
   if (hd == 128) {
     if (wide) DGI_DECODE(128, 8);
     else DGI_DECODE(128, 4);
     DGI_CHECK_LAUNCH();
     if (max_splits > 1 && counters == nullptr) {
-      decode_reduce_kernel<128><<<dim3(B, nh), 128, 0, s>>>(part_o, part_lse, context_lens,
-                                                            (uint16_t*)out, out_stride, max_splits,
-                                                            nh, part_size);
+      DGI_DECODE_REDUCE(128);
       DGI_CHECK_LAUNCH();
     }
   } else if (hd == 64) {
@@ -485,14 +517,15 @@ extern "C" int dgi_paged_decode(const void* q, int q_stride, const void* k_cache
     else DGI_DECODE(64, 4);
     DGI_CHECK_LAUNCH();
     if (max_splits > 1 && counters == nullptr) {
-      decode_reduce_kernel<64><<<dim3(B, nh), 64, 0, s>>>(part_o, part_lse, context_lens,
-                                                          (uint16_t*)out, out_stride, max_splits,
-                                                          nh, part_size);
+      DGI_DECODE_REDUCE(64);
       DGI_CHECK_LAUNCH();
     }
   } else {
     return -5;
   }
 #undef DGI_DECODE
+#undef DGI_DECODE_REDUCE
+#undef DGI_DECODE_CFG
+#undef DGI_DECODE_ARGS
   return 0;
 }

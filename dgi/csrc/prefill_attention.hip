@@ -22,6 +22,11 @@
 //   Optional tree mask: for EAGLE verification the last `tree_n` queries of a
 //   sequence see the cached prefix plus their ancestors, given as one 64-bit
 //   ancestor mask per query (built by tree.hip).
+//   Sliding window (WIN instantiations, window W > 0, never with a tree): the query at
+//   position p sees keys (p - W, p].  The workgroup's K/V loop starts at the 64-key tile of
+//   its first row's window start, a wave skips tiles that end before its own first row's
+//   window, and every other tile that is not inside all of the wave's windows takes the
+//   masked path.  window == 0 launches the WIN = false instantiations: today's code.
 #include <type_traits>
 
 #include "common.h"
@@ -61,15 +66,15 @@ constexpr int KT = 64;  // keys per tile
 // load_tile_fast fetch 8 codes per chunk with 8-byte loads and store_tile widens them to bf16
 // (exact) before the LDS stores; everything after the LDS image is the bf16 kernel's.  The
 // trailing argument is kv_scale [2, nkv] fp32: the head's K scale multiplies the softmax scale,
-// its V scale the final normalisation.
-template <int HD, int NW, int DB, bool FP8, typename... S>
+// its V scale the final normalisation.  WIN puts the window in front of it.
+template <int HD, int NW, int DB, bool FP8, bool WIN, typename... S>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
     const uint16_t* __restrict__ q, int q_stride, const uint16_t* __restrict__ k_cache,
     const uint16_t* __restrict__ v_cache, const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ cu_seqlens_q, const int* __restrict__ context_lens,
     const int* __restrict__ tiles, uint16_t* __restrict__ out, int out_stride, int nh, int nkv,
     int bs_log2, float scale_log2, const unsigned long long* __restrict__ tree_mask, int tree_n,
-    S... kv_scale) {
+    S... extra) {
   __shared__ __attribute__((aligned(16))) uint16_t lds[(DB ? 2 : 1) * 2 * KT * HD];
 
   const int b = tiles[2 * blockIdx.x];
@@ -78,7 +83,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
   const int kvh = head / (nh / nkv);
   [[maybe_unused]] float v_scale = 1.f;
   if constexpr (FP8) {
-    const float* sc = pack_ptr(kv_scale...);
+    const float* sc = pack_ptr(extra...);
     scale_log2 *= sc[kvh];
     v_scale = sc[nkv + kvh];
   }
@@ -128,6 +133,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
 
   const int last_row = min(t0 + 32 * NW, qlen) - 1;
   const int kv_end = min(ctx, pos_base + last_row + 1);
+  int window = 0;
+  if constexpr (WIN) window = pack_window(extra...);
+  // first K/V tile: the one that holds the window start of the workgroup's first row (the
+  // lowest of its rows'); t0 < qlen, so kv_start <= pos_base + t0 < kv_end
+  const int kv_start = WIN ? (max(0, pos_base + t0 - window + 1) & ~63) : 0;
 
   float m_run = -1e30f, l_run = 0.f;
   f32x16 o[ND];
@@ -216,10 +226,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
       load_tile(kb0);
     }
   };
-  if (kv_end > 0) load_any(0);
-  if (DB && kv_end > 0) {
+  if (kv_end > kv_start) load_any(kv_start);
+  if (DB && kv_end > kv_start) {
     store_tile(lds, lds + KT * HD);             // stage 0 <- tile 0
-    if (KT < kv_end) load_any(KT);              // registers <- tile 1
+    if (kv_start + KT < kv_end) load_any(kv_start + KT);   // registers <- tile 1
   }
   // last key this wave can see (causal); tiles beyond it are skipped
   const int wave_last_pos = pos_base + min(t0 + 32 * w + 31, qlen - 1);
@@ -228,7 +238,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
   const bool wave_tree = tree_mask != nullptr && (t0 + 32 * w + 31 >= tree_first);
   const bool wave_rows = t0 + 32 * w < qlen;
   int it = 0;
-  for (int kb0 = 0; kb0 < kv_end; kb0 += KT, ++it) {
+  for (int kb0 = kv_start; kb0 < kv_end; kb0 += KT, ++it) {
     uint16_t* ks;
     uint16_t* vs;
     if (DB) {
@@ -257,6 +267,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
     // whole tile above this wave's diagonal, or no valid query row in this wave
     // (it still stages K/V for the others)
     if (kb0 > wave_last_pos || !wave_rows) continue;
+    // whole tile before the window of this wave's first row, so before every row's
+    if (WIN && kb0 + KT - 1 <= wave_first_pos - window) continue;
 
     // ---- S^T = K Q^T for two 32-key blocks
     f32x16 sc[2];
@@ -273,13 +285,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
     // ---- online softmax; lane owns query lr, keys kb0 + 32kb + (r&3) + 8(r>>2) + 4hh.
     // Interior tiles (every key visible to every row of this wave, no tree rows) skip the
     // per-element mask; both kinds then share one exponent path.
-    const bool interior = (kb0 + KT <= kv_end) && (kb0 + KT - 1 <= wave_first_pos) && !wave_tree;
+    // (WIN: and the tile's first key inside the window of the wave's last row, the highest)
+    const bool interior = (kb0 + KT <= kv_end) && (kb0 + KT - 1 <= wave_first_pos) && !wave_tree &&
+                          !(WIN && kb0 <= wave_first_pos + 31 - window);
     if (!interior) {
       // masked keys -> -inf in raw score units, in place (one select per element, no branches:
       // the tree bit is read with a clamped shift and applied by mask).  -inf, not a large
       // finite value: a lane whose keys are all masked must get max -inf (no rescale) and
       // P = 2^(-inf) = 0, whatever the scale.  Causal-only tiles (the diagonal) skip the
-      // 64-bit tree-mask shifts.
+      // 64-bit tree-mask shifts.  A window masks the same way (key > my_pos - W): a late row of
+      // a tile wider than the window meets tiles with none of its keys; its max stays at the
+      // finite floor, every P is 2^(-inf) = 0 and the row accumulates exactly nothing.
       const int lim = row_valid ? min(my_pos, kv_end - 1) : -1;    // last visible key
       const int key0 = kb0 + 4 * hh;
       if (wave_tree) {
@@ -297,8 +313,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void prefill_attn_kernel(
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            sc[kb][r] = (key0 + 32 * kb + (r & 3) + 8 * (r >> 2) <= lim) ? sc[kb][r] : -__builtin_inff();
+          for (int r = 0; r < 16; ++r) {
+            const int key = key0 + 32 * kb + (r & 3) + 8 * (r >> 2);
+            const bool ok = WIN ? (key <= lim) & (key > my_pos - window) : key <= lim;
+            sc[kb][r] = ok ? sc[kb][r] : -__builtin_inff();
+          }
       }
     }
     float mx = -1e30f;
@@ -401,7 +420,11 @@ extern "C" int dgi_paged_prefill(const void* q, int q_stride, const void* k_cach
                                  const int* cu_seqlens_q, const int* context_lens, const int* tiles,
                                  int n_tiles, void* out, int out_stride, int nh, int nkv, int hd,
                                  int block_size, float scale, const unsigned long long* tree_mask,
-                                 int tree_n, int tile_rows, const float* kv_scale, hipStream_t s) {
+                                 int tree_n, int tile_rows, const float* kv_scale, int window,
+                                 hipStream_t s) {
+  if (window < 0) return -8;
+  // tree positions are not row indices: a window over them would mask the wrong keys
+  if (window > 0 && tree_mask != nullptr && tree_n > 0) return -9;
   if (n_tiles == 0) return 0;
   if (hd != 128 && hd != 64) return -5;
   if (nh % nkv) return -2;
@@ -413,19 +436,25 @@ extern "C" int dgi_paged_prefill(const void* q, int q_stride, const void* k_cach
   const int db = (tile_rows >> 16) & 1;          // bit 16: two LDS stages (prefill_attn_kernel DB)
   tile_rows &= 0xffff;
   if (tile_rows != 128 && tile_rows != 256) return -7;
-  // kv_scale != nullptr: the caches hold e4m3 codes
-#define DGI_PREFILL(HDV, NWV, DBV)                                                                     \
-  do {                                                                                                 \
-    if (kv_scale)                                                                                      \
-      prefill_attn_kernel<HDV, NWV, DBV, true, const float*><<<dim3(n_tiles, nh), NWV * 64, 0, s>>>(   \
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,            \
-          block_tables, bt_stride, cu_seqlens_q, context_lens, tiles, (uint16_t*)out, out_stride, nh,  \
-          nkv, bs_log2, scale_log2, tree_mask, tree_n, kv_scale);                                      \
-    else                                                                                               \
-      prefill_attn_kernel<HDV, NWV, DBV, false><<<dim3(n_tiles, nh), NWV * 64, 0, s>>>(                \
-          (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache,            \
-          block_tables, bt_stride, cu_seqlens_q, context_lens, tiles, (uint16_t*)out, out_stride, nh,  \
-          nkv, bs_log2, scale_log2, tree_mask, tree_n);                                                \
+  // kv_scale != nullptr: the caches hold e4m3 codes; window > 0: the WIN instantiations
+#define DGI_PREFILL_ARGS                                                                             \
+  (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,    \
+      bt_stride, cu_seqlens_q, context_lens, tiles, (uint16_t*)out, out_stride, nh, nkv, bs_log2,    \
+      scale_log2, tree_mask, tree_n
+#define DGI_PREFILL_CFG(NWV) <<<dim3(n_tiles, nh), NWV * 64, 0, s>>>
+#define DGI_PREFILL(HDV, NWV, DBV)                                                                   \
+  do {                                                                                               \
+    if (window > 0 && kv_scale)                                                                      \
+      prefill_attn_kernel<HDV, NWV, DBV, true, true, int, const float*> DGI_PREFILL_CFG(NWV)(        \
+          DGI_PREFILL_ARGS, window, kv_scale);                                                       \
+    else if (window > 0)                                                                             \
+      prefill_attn_kernel<HDV, NWV, DBV, false, true, int> DGI_PREFILL_CFG(NWV)(DGI_PREFILL_ARGS,    \
+                                                                                window);             \
+    else if (kv_scale)                                                                               \
+      prefill_attn_kernel<HDV, NWV, DBV, true, false, const float*> DGI_PREFILL_CFG(NWV)(            \
+          DGI_PREFILL_ARGS, kv_scale);                                                               \
+    else                                                                                             \
+      prefill_attn_kernel<HDV, NWV, DBV, false, false> DGI_PREFILL_CFG(NWV)(DGI_PREFILL_ARGS);       \
   } while (0)
   if (hd == 128) {
     if (tile_rows == 256) { if (db) DGI_PREFILL(128, 8, 1); else DGI_PREFILL(128, 8, 0); }
@@ -435,6 +464,8 @@ extern "C" int dgi_paged_prefill(const void* q, int q_stride, const void* k_cach
     else { if (db) DGI_PREFILL(64, 4, 1); else DGI_PREFILL(64, 4, 0); }
   }
 #undef DGI_PREFILL
+#undef DGI_PREFILL_CFG
+#undef DGI_PREFILL_ARGS
   DGI_CHECK_LAUNCH();
   return 0;
 }

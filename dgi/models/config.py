@@ -1,4 +1,4 @@
-"""Model configurations (Llama-3 8B/70B, Qwen2.5 7B/0.5B, Qwen3 0.6B/8B/32B, Qwen3-30B-A3B (MoE), GLM-4-9B, OPT-125m, tiny test models).
+"""Model configurations (Llama-3 8B/70B, Mistral-7B, Qwen2.5 7B/0.5B, Qwen3 0.6B/8B/32B, Qwen3-30B-A3B (MoE), GLM-4-9B, OPT-125m, tiny test models).
 
 Mirrors the fields the reference reads from HF ``AutoConfig``
 (worker/distributed/model_shard.py:273-311 uses hidden_size,
@@ -44,6 +44,23 @@ class ModelConfig:
     num_experts_per_tok: int = 0
     moe_intermediate_size: int = 0
     norm_topk_prob: bool = False      # renormalise the k chosen probabilities to sum to one
+    # Sliding-window attention (Mistral, Qwen2): a query at position p of a windowed layer sees keys
+    # j with p - sliding_window < j <= p (HF's rule); 0 = every layer attends over the whole context.
+    # window_layers: the global indices of the layers that slide; None with a window means all.
+    sliding_window: int = 0
+    window_layers: Optional[tuple] = None
+
+    def window_of(self, global_layer: int) -> int:
+        """The window of layer ``global_layer`` (index in the whole model); 0 = full attention."""
+        if self.sliding_window <= 0:
+            return 0
+        if self.window_layers is None or global_layer in self.window_layers:
+            return self.sliding_window
+        return 0
+
+    @property
+    def has_window(self) -> bool:
+        return any(self.window_of(li) for li in range(self.num_layers))
 
     @property
     def is_moe(self) -> bool:
@@ -134,6 +151,29 @@ class ModelConfig:
             bad = sorted({t for t in (d.get("layer_types") or []) if t != "full_attention"})
             if bad:
                 raise ValueError(f"{name}: Qwen3 layer_types {bad} are not supported (full_attention only)")
+        # Mistral slides on every layer, Qwen2 (with use_sliding_window) on layers >= max_window_layers;
+        # an explicit layer_types list wins for both
+        win = {}
+        if mt in ("mistral", "qwen2"):
+            L = d["num_hidden_layers"]
+            W = int(d.get("sliding_window") or 0)
+            if W < 0:
+                raise ValueError(f"{name}: sliding_window {W} is negative")
+            lt = d.get("layer_types")
+            if lt:
+                bad = sorted({t for t in lt if t not in ("full_attention", "sliding_attention")})
+                if bad or len(lt) != L:
+                    raise ValueError(f"{name}: layer_types must name full_attention / sliding_attention for each "
+                                     f"of the {L} layers, got {lt}")
+                slide = tuple(i for i, t in enumerate(lt) if t == "sliding_attention")
+                if slide and W == 0:
+                    raise ValueError(f"{name}: sliding_attention layers without a sliding_window")
+            elif mt == "mistral":
+                slide = tuple(range(L)) if W else ()
+            else:
+                slide = tuple(range(int(d.get("max_window_layers", L)), L)) if d.get("use_sliding_window") and W else ()
+            if slide:
+                win = dict(sliding_window=W, window_layers=None if len(slide) == L else slide)
         hd = d.get("head_dim") or H // nh
         prf = d.get("partial_rotary_factor", rp.get("partial_rotary_factor", 1.0))
         rot = int(hd * prf) if prf and prf < 1.0 else None
@@ -148,7 +188,7 @@ class ModelConfig:
                            qkv_bias=bool(d.get("attention_bias", mt == "qwen2")),
                            rotary_dim=rot, rope_interleaved=(mt == "glm"),
                            qk_norm=(mt in ("qwen3", "qwen3_moe")), bos_token_id=d.get("bos_token_id", 1),
-                           eos_token_id=eos, **moe)
+                           eos_token_id=eos, **moe, **win)
 
     @staticmethod
     def from_file(path: str) -> "ModelConfig":
@@ -173,6 +213,17 @@ PRESETS: dict[str, ModelConfig] = {
     "llama-tiny-tp": ModelConfig(name="llama-tiny-tp", vocab_size=1024, hidden_size=1024, intermediate_size=2048,
                                  num_layers=2, num_heads=8, num_kv_heads=2, head_dim=128, max_position=4096,
                                  bos_token_id=1, eos_token_id=2),
+    # Mistral-7B-v0.1: the Llama block with a 4096-token sliding window on every layer.  Shapes as the
+    # published config is remembered; it could not be checked offline, and a local config.json always
+    # takes precedence.
+    "mistral-7b": ModelConfig(name="mistral-7b", vocab_size=32000, hidden_size=4096, intermediate_size=14336,
+                              num_layers=32, num_heads=32, num_kv_heads=8, head_dim=128, rope_theta=10000.0,
+                              rms_eps=1e-5, max_position=32768, sliding_window=4096, bos_token_id=1,
+                              eos_token_id=2),
+    # tiny Mistral for tests: a 40-token window on both layers
+    "mistral-tiny": ModelConfig(name="mistral-tiny", vocab_size=1024, hidden_size=1024, intermediate_size=2048,
+                                num_layers=2, num_heads=8, num_kv_heads=2, head_dim=128, rope_theta=10000.0,
+                                max_position=4096, sliding_window=40, bos_token_id=1, eos_token_id=2),
     # Qwen2 / Qwen2.5 family (the reference's default LLM is Qwen2.5-7B-Instruct):
     # Llama block + biased QKV, GQA 7:1 (7B) / 7:1 (0.5B), theta 1e6
     "qwen2.5-7b": ModelConfig(name="qwen2.5-7b", arch="qwen2", vocab_size=152064, hidden_size=3584,
@@ -188,6 +239,12 @@ PRESETS: dict[str, ModelConfig] = {
                              intermediate_size=1536, num_layers=2, num_heads=14, num_kv_heads=2, head_dim=128,
                              rope_theta=1000000.0, rms_eps=1e-6, max_position=4096, tie_embeddings=True,
                              qkv_bias=True, bos_token_id=1, eos_token_id=2),
+    # qwen-tiny with a 40-token window on layer 1 only (Qwen2's max_window_layers = 1)
+    "qwen-tiny-swa": ModelConfig(name="qwen-tiny-swa", arch="qwen2", vocab_size=1024, hidden_size=1024,
+                                 intermediate_size=1536, num_layers=2, num_heads=14, num_kv_heads=2, head_dim=128,
+                                 rope_theta=1000000.0, rms_eps=1e-6, max_position=4096, tie_embeddings=True,
+                                 qkv_bias=True, sliding_window=40, window_layers=(1,), bos_token_id=1,
+                                 eos_token_id=2),
     # Qwen3 dense family: the Llama block with no QKV bias, an explicit head_dim of 128 (q_size !=
     # hidden_size on 0.6B and 32B) and an RMSNorm over each q / k head before RoPE.  Shapes as the
     # published configs are remembered; they could not be checked offline, and a local config.json
@@ -243,6 +300,7 @@ ALIASES = {
     "meta-llama/Llama-3.1-8B-Instruct": "llama3-8b",
     "meta-llama/Meta-Llama-3-70B": "llama3-70b",
     "meta-llama/Meta-Llama-3-70B-Instruct": "llama3-70b",
+    "mistralai/Mistral-7B-v0.1": "mistral-7b",
     "facebook/opt-125m": "opt-125m",
     "Qwen/Qwen2.5-7B-Instruct": "qwen2.5-7b",
     "Qwen/Qwen2.5-7B": "qwen2.5-7b",
@@ -260,7 +318,8 @@ ALIASES = {
 def get_config(name_or_path: str) -> ModelConfig:
     """Preset, alias, HF config dir/file, or a family guess from the name.
     ``<model>@L<n>`` keeps the architecture and truncates it to ``n`` layers
-    (multi-rank rehearsals of a big model's shapes on one GPU)."""
+    (multi-rank rehearsals of a big model's shapes on one GPU); sliding-window layers keep
+    their windows by global index."""
     if "@L" in name_or_path:
         base, n = name_or_path.rsplit("@L", 1)
         return dataclasses.replace(get_config(base), name=name_or_path, num_layers=int(n))

@@ -517,6 +517,8 @@ class LlamaModel:
         if out is None:
             out = torch.empty(T, c.q_size, device=qkv.device, dtype=qkv.dtype)
         nd = meta.num_decode
+        # this layer's sliding window (0 = full attention); a captured graph bakes it in
+        window = c.window_of(self.layer_start + li)
         # mixed step: the decode rows' split-KV attention (HBM-latency bound) runs on a side
         # stream beside the prefill rows' flash attention; joined before the o-proj
         side = None
@@ -532,11 +534,12 @@ class LlamaModel:
             with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
                 ops.paged_decode(qkv[:nd], kc, vc, meta.dec_block_tables, meta.dec_context_lens, c.num_heads,
                                  c.num_kv_heads, self.scale, meta.dec_max_splits, meta.dec_part_size,
-                                 out=out[:nd], workspace=meta.dec_workspace, kv_scale=ksc)
+                                 out=out[:nd], workspace=meta.dec_workspace, kv_scale=ksc, window=window)
         if meta.num_prefill_tokens > 0:
             ops.paged_prefill(qkv[nd:], kc, vc, meta.pre_block_tables, meta.pre_cu_seqlens, meta.pre_context_lens,
                               c.num_heads, c.num_kv_heads, self.scale, tiles=meta.pre_tiles,
-                              tree_mask=meta.tree_mask, tree_n=meta.tree_n, out=out[nd:], kv_scale=ksc)
+                              tree_mask=meta.tree_mask, tree_n=meta.tree_n, out=out[nd:], kv_scale=ksc,
+                              window=window)
         if side is not None:
             main.wait_stream(side)
         return out

@@ -308,7 +308,16 @@ def _gather_kv(k_cache, v_cache, bt_row, ctx, kv_scale=None):
     return k, v
 
 
-def paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale, kv_scale=None) -> torch.Tensor:
+def _check_window(window, what: str) -> int:
+    if window < 0:
+        raise ValueError(f"{what}: window must be >= 0 (0 = full attention), got {window}")
+    return int(window)
+
+
+def paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale, kv_scale=None,
+                     window: int = 0) -> torch.Tensor:
+    """``window > 0``: the row at position ``ctx - 1`` sees the last ``window`` keys only."""
+    window = _check_window(window, "paged_decode_ref")
     hd = k_cache.shape[-1]
     B = q.shape[0]
     out = torch.empty(B, nh * hd, dtype=q.dtype, device=q.device)
@@ -318,6 +327,8 @@ def paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, s
         k, v = _gather_kv(k_cache, v_cache, block_tables[b], ctx, kv_scale)
         qb = q[b, : nh * hd].float().view(nkv, G, hd)
         s = torch.einsum("hgd,thd->hgt", qb, k.float()) * scale
+        if 0 < window < ctx:
+            s[..., : ctx - window] = float("-inf")
         p = torch.softmax(s, dim=-1)
         o = torch.einsum("hgt,thd->hgd", p, v.float())
         out[b] = o.reshape(nh * hd).to(q.dtype)
@@ -340,8 +351,12 @@ def decode_split_plan(batch: int, max_ctx: int, nkv: int, num_cus: int = 256) ->
 
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale,
                  max_splits: int = 1, part_size: int = 1 << 30, out=None, workspace=None,
-                 kv_scale=None) -> torch.Tensor:
+                 kv_scale=None, window: int = 0) -> torch.Tensor:
     """Single-token attention for each row of ``q`` over its paged context.
+
+    ``window > 0`` (sliding-window layers): a row sees its last ``window`` keys, its own
+    included; the split plan then covers ``[max(0, ctx - window) & ~31, ctx)`` and no K/V slot
+    before that is read.  ``window == 0`` launches the unwindowed kernels.
 
     ``part_size > 0``: fixed parts; ``max_splits``/``part_size`` must cover the
     longest context (``decode_split_plan``).  ``part_size <= 0``: device-side
@@ -352,6 +367,7 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale
     combines the splits (no reduce kernel).  An fp8 cache (``float8_e4m3fn``) is read as
     e4m3 codes times ``kv_scale`` (the layer's ``[2, n_kv]`` fp32 scales; ones if None).
     """
+    window = _check_window(window, "paged_decode")
     if _native(q):
         hd = k_cache.shape[-1]
         B = q.shape[0]
@@ -370,9 +386,9 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale
             if part_size > 0:
                 part_size = max(128, ((part_size if part_size < (1 << 30) else 1 << 20) + 127) // 128 * 128)
         _call("paged_decode", out, q, k_cache, v_cache, block_tables, context_lens, po, pl,
-              nh, nkv, max_splits, part_size, scale, cnt, _kv_scale_for(k_cache, kv_scale, "paged_decode"))
+              nh, nkv, max_splits, part_size, scale, cnt, _kv_scale_for(k_cache, kv_scale, "paged_decode"), window)
         return out
-    r = paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale, kv_scale)
+    r = paged_decode_ref(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale, kv_scale, window)
     if out is not None:
         out.copy_(r)
         return out
@@ -380,7 +396,11 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, nh, nkv, scale
 
 
 def paged_prefill_ref(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens, nh, nkv, scale,
-                      tree_mask=None, tree_n: int = 0, kv_scale=None) -> torch.Tensor:
+                      tree_mask=None, tree_n: int = 0, kv_scale=None, window: int = 0) -> torch.Tensor:
+    """``window > 0``: the query at position p sees keys j with p - window < j <= p."""
+    window = _check_window(window, "paged_prefill_ref")
+    if window > 0 and tree_mask is not None and tree_n > 0:
+        raise ValueError("paged_prefill_ref: a sliding window cannot be combined with a tree mask")
     hd = k_cache.shape[-1]
     T = q.shape[0]
     out = torch.zeros(T, nh * hd, dtype=q.dtype, device=q.device)
@@ -398,6 +418,8 @@ def paged_prefill_ref(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_l
         qpos = torch.arange(ctx - ql, ctx, device=q.device)
         kpos = torch.arange(ctx, device=q.device)
         allow = kpos[None, :] <= qpos[:, None]
+        if 0 < window < ctx:
+            allow &= kpos[None, :] > qpos[:, None] - window
         if tree_mask is not None and tree_n > 0:
             tf = ql - tree_n
             key0 = ctx - ql + tf
@@ -428,7 +450,8 @@ def order_prefill_tiles(cu_seqlens_q, context_lens=None, tile: int = 0) -> np.nd
     qlen + t0 + tile, so in (sequence, row) order the longest workgroups of the last heads
     are dispatched last and run alone at the end of the grid; longest-first ordering lets
     the short ones fill in behind them (the grid is (tiles, heads): every head walks the
-    same order).  Ties keep (sequence, row) order."""
+    same order).  Ties keep (sequence, row) order.  The estimate is the full-attention one
+    for sliding-window layers too: tiles are built once per step for all layers."""
     tile = tile or PREFILL_TILE
     cu = np.asarray(cu_seqlens_q, np.int64)
     nb = len(cu) - 1
@@ -452,9 +475,15 @@ def prefill_tiles(cu_seqlens_q: list[int], tile: int = 0, context_lens=None) -> 
 
 
 def paged_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens, nh, nkv, scale,
-                  tiles=None, tree_mask=None, tree_n: int = 0, out=None, kv_scale=None) -> torch.Tensor:
+                  tiles=None, tree_mask=None, tree_n: int = 0, out=None, kv_scale=None,
+                  window: int = 0) -> torch.Tensor:
     """Causal varlen attention of packed queries over the paged KV (prefix + new).  An fp8 cache
-    is read as e4m3 codes times ``kv_scale`` (``[2, n_kv]`` fp32; ones if None)."""
+    is read as e4m3 codes times ``kv_scale`` (``[2, n_kv]`` fp32; ones if None).  ``window > 0``
+    (sliding-window layers): the query at position p sees keys (p - window, p]; no K/V slot before
+    the 64-key tile of the sequence's first window start is read; not with a tree mask."""
+    window = _check_window(window, "paged_prefill")
+    if window > 0 and tree_mask is not None and tree_n > 0:
+        raise ValueError("paged_prefill: a sliding window cannot be combined with a tree mask")
     if _native(q) and k_cache.shape[-1] not in (64, 128):
         _warn_once("paged_prefill", f"head_dim {k_cache.shape[-1]}: the MFMA prefill kernel is built for 64 / 128; "
                                     "using the PyTorch reference")
@@ -467,10 +496,10 @@ def paged_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens,
             tiles = torch.tensor(tl if tl else [[0, 0]], dtype=torch.int32, device=q.device)[: len(tl)]
         _call("paged_prefill", out, q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens,
               tiles, nh, nkv, scale, tree_mask, tree_n,
-              PREFILL_TILE | ((PREFILL_DB & 1) << 16), _kv_scale_for(k_cache, kv_scale, "paged_prefill"))
+              PREFILL_TILE | ((PREFILL_DB & 1) << 16), _kv_scale_for(k_cache, kv_scale, "paged_prefill"), window)
         return out
     r = paged_prefill_ref(q, k_cache, v_cache, block_tables, cu_seqlens_q, context_lens, nh, nkv, scale,
-                          tree_mask, tree_n, kv_scale)
+                          tree_mask, tree_n, kv_scale, window)
     if out is not None:
         out.copy_(r)
         return out

@@ -96,11 +96,22 @@ def default_feature_layers(num_layers: int) -> tuple:
     return (lo, num_layers // 2, max(num_layers - 3, 0))
 
 
+def refuse_windows(model_cfg: ModelConfig) -> None:
+    """Tree verification attends through a tree mask, whose node positions are not row indices, so
+    the attention kernel refuses a window beside it; a target with a sliding-window layer is
+    refused when the speculative engine or its draft is built."""
+    if model_cfg.has_window:
+        raise ValueError(f"EAGLE-3 speculation does not support sliding-window attention: {model_cfg.name} has "
+                         f"windowed layers (sliding_window={model_cfg.sliding_window}); serve it from a plain "
+                         "LLMEngine")
+
+
 class Eagle3Draft:
     """One-layer EAGLE-3 draft decoder sharing the target's embedding / LM head."""
 
     def __init__(self, target: LlamaModel, num_blocks: int, block_size: int, seed: int = 1234):
         c = target.cfg
+        refuse_windows(c)
         self.target = target
         self.cfg = c
         dev, dt = target.device, target.dtype
@@ -770,7 +781,11 @@ class SpecEngine(LLMEngine):
     def __init__(self, cfg: EngineConfig, spec: Optional[SpecConfig] = None, model_cfg: Optional[ModelConfig] = None,
                  model=None, draft: Optional[Eagle3Draft] = None):
         refuse_fp8_kv(cfg, "EAGLE-3 speculation")
+        known = model_cfg or getattr(model, "cfg", None)
+        if known is not None:
+            refuse_windows(known)
         super().__init__(cfg, model_cfg, model)
+        refuse_windows(self.model_cfg)
         self.spec = spec or SpecConfig()
         self.spec.validate()
         L = self.model_cfg.num_layers

@@ -9,6 +9,11 @@ Every row also times the same problem on an fp8 KV cache (e4m3 pages, per-head s
 
 ATTN_HEADS="32,8" picks another head geometry (nh,nkv); ATTN_PREFILL="8x512,1x8192" and
 ATTN_DECODE="512x576,768x576" pick the (B x L) / (B x C) shapes.
+
+``--window W`` adds the sliding-window kernels on the same problem (bf16 pages): ``win_us`` with
+a split plan made for the window's span, ``win_ctxplan_us`` (decode) with the plan of the whole
+context, which is what a model whose layers share one step plan passes; ``--no-sdpa`` skips the
+dense torch reference (long prompts).
 """
 import json
 import math
@@ -23,6 +28,8 @@ import torch.nn.functional as F
 from dgi import ops
 
 nh, nkv, hd, bs = 64, 8, 128, 16
+WINDOW = int(sys.argv[sys.argv.index("--window") + 1]) if "--window" in sys.argv else 0
+SDPA = "--no-sdpa" not in sys.argv
 if os.environ.get("ATTN_HEADS"):
     nh, nkv = (int(x) for x in os.environ["ATTN_HEADS"].split(","))
 dev = "cuda"
@@ -72,14 +79,20 @@ def prefill(B, L):
     k8, v8, sc = fp8_pages(kc, vc)
     us8 = timed(lambda: ops.paged_prefill(q, k8, v8, bt, cu, ctx, nh, nkv, scale, tiles=tiles, out=out, kv_scale=sc))
     flops = 4 * nh * hd * B * L * L / 2
-    qd = torch.randn(B, nh, L, hd, device=dev, dtype=torch.bfloat16)
-    kd = torch.randn(B, nh, L, hd, device=dev, dtype=torch.bfloat16)
-    vd = torch.randn_like(kd)
-    us_sdpa = timed(lambda: F.scaled_dot_product_attention(qd, kd, vd, is_causal=True))
-    return {"kernel": "prefill", "B": B, "L": L, "tile": ops.PREFILL_TILE, "db": ops.PREFILL_DB,
-            "order": os.environ.get("ATTN_TILE_ORDER", "1"), "us": round(us, 1),
-            "TFLOPs": round(flops / us / 1e6, 1), "fp8_us": round(us8, 1), "fp8_TFLOPs": round(flops / us8 / 1e6, 1),
-            "sdpa_us": round(us_sdpa, 1), "sdpa_TFLOPs": round(flops / us_sdpa / 1e6, 1)}
+    row = {"kernel": "prefill", "B": B, "L": L, "tile": ops.PREFILL_TILE, "db": ops.PREFILL_DB,
+           "order": os.environ.get("ATTN_TILE_ORDER", "1"), "us": round(us, 1),
+           "TFLOPs": round(flops / us / 1e6, 1), "fp8_us": round(us8, 1), "fp8_TFLOPs": round(flops / us8 / 1e6, 1)}
+    if WINDOW:
+        usw = timed(lambda: ops.paged_prefill(q, kc, vc, bt, cu, ctx, nh, nkv, scale, tiles=tiles, out=out,
+                                              window=WINDOW))
+        row.update(window=WINDOW, win_us=round(usw, 1), win_speedup=round(us / usw, 3))
+    if SDPA:
+        qd = torch.randn(B, nh, L, hd, device=dev, dtype=torch.bfloat16)
+        kd = torch.randn(B, nh, L, hd, device=dev, dtype=torch.bfloat16)
+        vd = torch.randn_like(kd)
+        us_sdpa = timed(lambda: F.scaled_dot_product_attention(qd, kd, vd, is_causal=True))
+        row.update(sdpa_us=round(us_sdpa, 1), sdpa_TFLOPs=round(flops / us_sdpa / 1e6, 1))
+    return row
 
 
 def decode(B, C):
@@ -99,9 +112,17 @@ def decode(B, C):
     us8 = timed(lambda: ops.paged_decode(q, k8, v8, bt, ctx, nh, nkv, scale, splits, part, out=out, workspace=ws,
                                          kv_scale=sc))
     byts = B * C * nkv * hd * 2 * 2
-    return {"kernel": "decode", "nh": nh, "nkv": nkv, "B": B, "C": C, "splits": splits, "us": round(us, 1),
-            "KV_TBs": round(byts / us / 1e6, 2), "fp8_us": round(us8, 1), "fp8_KV_TBs": round(byts / 2 / us8 / 1e6, 2),
-            "fp8_speedup": round(us / us8, 3)}
+    row = {"kernel": "decode", "nh": nh, "nkv": nkv, "B": B, "C": C, "splits": splits, "us": round(us, 1),
+           "KV_TBs": round(byts / us / 1e6, 2), "fp8_us": round(us8, 1), "fp8_KV_TBs": round(byts / 2 / us8 / 1e6, 2),
+           "fp8_speedup": round(us / us8, 3)}
+    if WINDOW:
+        wsplits, wpart = ops.decode_split_plan(B, min(C, WINDOW + 31), nkv)
+        usw = timed(lambda: ops.paged_decode(q, kc, vc, bt, ctx, nh, nkv, scale, wsplits, wpart, out=out, workspace=ws,
+                                             window=WINDOW))
+        usc = timed(lambda: ops.paged_decode(q, kc, vc, bt, ctx, nh, nkv, scale, splits, part, out=out, workspace=ws,
+                                             window=WINDOW))
+        row.update(window=WINDOW, win_splits=wsplits, win_us=round(usw, 1), win_ctxplan_us=round(usc, 1))
+    return row
 
 
 if __name__ == "__main__":

@@ -20,6 +20,12 @@ unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
 ``DGI_W8A8_MIN_M`` rows, default 2048; ``quantization: "fp8"`` alone stays W8A16), ``expert_quant`` (``"fp8"``:
 weight-only e4m3 experts of a MoE model; anything else, or a dense model, is served with bf16 experts); nested ``sglang``/``vllm``/
 ``native`` dicts are merged in.
+
+Sliding-window attention needs no key: a Mistral config (``sliding_window`` on every layer) or a Qwen2
+config with ``use_sliding_window`` (layers from ``max_window_layers`` on, or an explicit ``layer_types``)
+is served with windowed attention kernels on those layers; the preset ``mistral-7b`` (alias
+``mistralai/Mistral-7B-v0.1``) has a 4,096-token window.  KV blocks that fell out of every window stay
+allocated.  Qwen3 windows and EAGLE-3 speculation on a windowed model are refused.
 """
 from __future__ import annotations
 

@@ -827,6 +827,7 @@ void topk(at::Tensor out_v, at::Tensor out_i, const at::Tensor& logits, int64_t 
   const int B = (int)logits.size(0);
   TORCH_CHECK(out_v.scalar_type() == at::kFloat && out_i.scalar_type() == at::kLong);
   TORCH_CHECK(out_v.numel() >= B * k && out_i.numel() >= B * k);
+  TORCH_CHECK(k <= logits.size(1), "topk: k above the row length");
   check_rc(dgi_topk(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B, (int)logits.size(1),
                     (int)logits.stride(0), (int)k, out_v.data_ptr<float>(),
                     reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()), cur_stream()),
@@ -840,6 +841,10 @@ void topk_logprobs(at::Tensor out_v, at::Tensor out_i, const at::Tensor& logits,
   const int B = (int)logits.size(0), V = (int)logits.size(1);
   TORCH_CHECK(out_v.scalar_type() == at::kFloat && out_i.scalar_type() == at::kLong);
   TORCH_CHECK(out_v.numel() >= B * k && out_i.numel() >= B * k && out_v.is_contiguous() && out_i.is_contiguous());
+  TORCH_CHECK(k <= V, "topk_logprobs: k above the row length");
+  // the kernels read 16-byte vectors from every row start
+  TORCH_CHECK(logits.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "topk_logprobs: rows must start on 16 bytes");
   at::Tensor ws = at::empty({std::max(1, dgi_topk_logprobs_ws_floats(B, V))}, logits.options().dtype(at::kFloat));
   check_rc(dgi_topk_logprobs(logits.data_ptr(), B, V, (int)logits.stride(0), (int)k, ws.data_ptr<float>(),
                              out_v.data_ptr<float>(), reinterpret_cast<long long*>(out_i.data_ptr<int64_t>()),

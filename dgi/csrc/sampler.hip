@@ -22,6 +22,20 @@ __device__ __forceinline__ uint32_t hash32(uint32_t x) {
   return x;
 }
 
+// Gumbel-max score of logit v at vocab id i: v / T - log(-log(u)), u the counter-based uniform
+// of (row seed, step, i).  u = (top 23 hash bits + 1/2) / 2^23: n + 0.5 has 24 significant bits,
+// so it is exact in fp32 and u lies in [2^-24, 1 - 2^-24].  (A 24-bit draw rounds (n + 0.5f) to
+// even above 2^23 and reaches u == 1.0f at n = 2^24 - 1, where the noise is +inf and that id wins
+// whatever its logit.)  ops._uniform_from_hash is the same draw on the CPU.
+__device__ __forceinline__ float hash_uniform(uint32_t h) {
+  return ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
+}
+
+__device__ __forceinline__ float gumbel_score(float v, float inv_t, uint32_t seed, int i) {
+  const float u = hash_uniform(hash32(seed ^ hash32((uint32_t)i + 0x9e3779b9u)));
+  return v * inv_t - __logf(-__logf(u));
+}
+
 template <typename T>
 __device__ __forceinline__ float load_logit(const T* p, int i);
 template <>
@@ -89,9 +103,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(const T* __restrict__ logi
     const float th = thresh ? thresh[row] : -INFINITY;
     scan_row<T>(lp, V, stride, [&](float v, int i) {
       if (v < th) return;  // outside the top-k / top-p set
-      const uint32_t h = hash32(seed ^ hash32((uint32_t)i + 0x9e3779b9u));
-      const float u = ((h >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      v = v * inv_t - __logf(-__logf(u));
+      v = gumbel_score(v, inv_t, seed, i);
       if (v > best || (v == best && i < best_i)) { best = v; best_i = i; }
     });
   }
@@ -149,9 +161,7 @@ __global__ __launch_bounds__(SP_NT) void sample_part_kernel(const T* __restrict_
     scan_row<T>(lp, n, stride, [&](float v, int i) {
       i += lo;
       if (v < th) return;
-      const uint32_t h = hash32(seed ^ hash32((uint32_t)i + 0x9e3779b9u));
-      const float u = ((h >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      v = v * inv_t - __logf(-__logf(u));
+      v = gumbel_score(v, inv_t, seed, i);
       if (v > best || (v == best && i < best_i)) { best = v; best_i = i; }
     });
   }
@@ -194,7 +204,8 @@ __global__ __launch_bounds__(64) void sample_final_kernel(const float* __restric
   if (lane == 0) out[row] = best_i == 0x7fffffff ? 0 : best_i;
 }
 
-// top-k (k <= 16) per row: values + indices, descending.  One 256-thread
+// top-k (k <= 16 and k <= V) per row: values + indices, descending, lower index first among
+// equal values (a -inf tail included).  One 256-thread
 // block per row; each thread keeps its own sorted top-k, then a tree merge in LDS.
 template <typename T>
 __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ logits, int V, int stride,
@@ -207,9 +218,13 @@ __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ logits,
 #pragma unroll
   for (int k = 0; k < 16; ++k) { tv[k] = -INFINITY; ti[k] = 0x7fffffff; }
   scan_row<T>(lp, V, stride, [&](float v, int i) {
-    if (v > tv[K - 1]) {
+    // a thread meets its indices in ascending order, so among equals the earlier entry stays
+    // ahead; only the empty slots (-inf, 0x7fffffff) give way to an equal value, a -inf logit
+    if (v > tv[K - 1] || (v == tv[K - 1] && i < ti[K - 1])) {
       int k = K - 1;
-      while (k > 0 && tv[k - 1] < v) { tv[k] = tv[k - 1]; ti[k] = ti[k - 1]; --k; }
+      while (k > 0 && (tv[k - 1] < v || (tv[k - 1] == v && ti[k - 1] > i))) {
+        tv[k] = tv[k - 1]; ti[k] = ti[k - 1]; --k;
+      }
       tv[k] = v; ti[k] = i;
     }
   });
@@ -393,9 +408,11 @@ __global__ __launch_bounds__(TK_NT) void topk_lse_final_kernel(int C, int K, con
   __shared__ int s_i[(TK_NT / 64) * KP];
   tk_block_reduce<KP>(tv, ti, m, sum, s_v, s_i, s_m, s_s);
   if (threadIdx.x == 0) {
-    const float lse = m + __logf(sum);
+    // (v - max) - log(sum): rounding once at the size of the log-prob, not of max + log(sum)
+    // (at |logits| ~ 3e4 an fp32 logsumexp has an ulp of 2e-3)
+    const float lsum = __logf(sum);
     for (int k = 0; k < K; ++k) {
-      out_v[(size_t)row * K + k] = tv[k] - lse;
+      out_v[(size_t)row * K + k] = (tv[k] - m) - lsum;
       out_i[(size_t)row * K + k] = ti[k];
     }
   }

@@ -1186,15 +1186,25 @@ def _hash32(x: torch.Tensor) -> torch.Tensor:
     return x ^ (x >> 16)
 
 
+def _uniform_from_hash(h: torch.Tensor) -> torch.Tensor:
+    """sampler.hip ``hash_uniform``: the top 23 bits of a 32-bit hash as the fp32 uniform
+    ``(n + 0.5) / 2^23``.  ``n + 0.5`` needs 24 significant bits, so every step is exact in
+    fp32 and u lies in [2^-24, 1 - 2^-24]: never 0 or 1, where the Gumbel noise
+    ``-log(-log(u))`` would be infinite (it stays within about [-2.8, 16.6])."""
+    return ((h >> 9).float() + 0.5) * (1.0 / 8388608.0)
+
+
 def gumbel_uniform(seeds: Optional[torch.Tensor], step: int, V: int, B: int) -> torch.Tensor:
     """The per-(row, vocab id) uniforms the HIP sampler draws: a counter-based
     hash of (row seed, step, token id), so a row's draw depends on its own seed
-    only (never on the batch it shares) and CPU and GPU pick the same tokens."""
+    only (never on the batch it shares) and CPU and GPU pick the same tokens
+    (tests/test_sampler_exact_gpu.py holds the kernel to that, up to fp32 rounding of
+    the noisy logits between two near-tied candidates)."""
     sd = seeds.long().cpu() if seeds is not None else torch.zeros(B, dtype=torch.long)
     row = ((sd * 2654435761) & _M32) ^ ((step * 40503) & _M32)
     ids = _hash32((torch.arange(V, dtype=torch.long) + 0x9E3779B9) & _M32)
     h = _hash32(row[:, None] ^ ids[None, :])
-    return ((h >> 8).float() + 0.5) * (1.0 / 16777216.0)
+    return _uniform_from_hash(h)
 
 
 def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None,
@@ -1231,27 +1241,42 @@ def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None,
 def topk_logprobs(logits: torch.Tensor, k: int):
     """Top-k (k <= 16) of ``log_softmax(logits.float())`` per row: fp32 log-probs and int64
     indices, descending (ties: lower index first).  Native path (k <= 8): two HIP kernels
-    straight from bf16 logits (sampler.hip: chunked top-k + logsumexp, then a per-row merge)."""
+    straight from bf16 logits (sampler.hip: chunked top-k + logsumexp, then a per-row merge).
+    They read 16-byte vectors, so a view whose rows do not start on 16 bytes (row stride not a
+    multiple of 8, or an offset base) takes ``topk`` of the logits (their order, not that of
+    the rounded log-probs) and subtracts the fp32 ``max + log(sum)`` as ``(v - max) - log(sum)``.
+    ``k`` outside 1..min(16, V) raises."""
+    if not 1 <= k <= min(16, logits.shape[-1]):
+        raise ValueError(f"topk_logprobs: k = {k} outside 1..min(16, V = {logits.shape[-1]})")
     if _native(logits) and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1 \
-            and logits.stride(0) % 8 == 0 and k <= 8:
+            and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0 and k <= 8:
         B = logits.shape[0]
         v = torch.empty(B, k, dtype=torch.float32, device=logits.device)
         i = torch.empty(B, k, dtype=torch.long, device=logits.device)
         _call("topk_logprobs", v, i, logits, k)
         return v, i
-    return topk(torch.log_softmax(logits.float(), dim=-1), k)
+    lf = logits.float()
+    m = lf.amax(dim=-1, keepdim=True)
+    lsum = torch.log(torch.exp(lf - m).sum(dim=-1, keepdim=True))
+    v, i = topk(logits, k)
+    return (v - m) - lsum, i
 
 
 def topk(logits: torch.Tensor, k: int):
-    """Top-k (k <= 16) values (fp32) and indices (int64), descending."""
+    """Top-k (k <= 16) values (fp32) and indices (int64), descending, the lower index first
+    among equal values (-inf included).  ``k`` outside 1..min(16, V) raises on either path: the
+    kernel keeps 16 candidates per thread, and a row has no k-th element beyond V (as
+    ``torch.topk``)."""
+    if not 1 <= k <= min(16, logits.shape[-1]):
+        raise ValueError(f"topk: k = {k} outside 1..min(16, V = {logits.shape[-1]})")
     if _native(logits):
         B = logits.shape[0]
         v = torch.empty(B, k, dtype=torch.float32, device=logits.device)
         i = torch.empty(B, k, dtype=torch.long, device=logits.device)
         _call("topk", v, i, logits, k)
         return v, i
-    v, i = logits.float().topk(k, dim=-1)
-    return v, i
+    v, i = logits.float().sort(dim=-1, descending=True, stable=True)    # torch.topk leaves the tie order open
+    return v[..., :k].contiguous(), i[..., :k].contiguous()
 
 
 # ----------------------------------------------------------------------------
@@ -1650,7 +1675,14 @@ def tree_verify_ref(parent, draft, target, anc, depth, max_path: int):
 
 
 def tree_verify(parent, draft, target, anc, depth, max_path: int):
-    """Greedy tree acceptance: (accept_len[B], path[B,max_path], tokens[B,max_path+1])."""
+    """Greedy tree acceptance: (accept_len[B], path[B,max_path], tokens[B,max_path+1]).
+
+    ``path[:accept_len + 1]`` are the node ids from the root to the deepest accepted node (lowest
+    index among equally deep ones), ``tokens[:accept_len]`` their draft tokens and
+    ``tokens[accept_len]`` the bonus token; the rest stays 0.  Precondition: the accepted depth
+    is below ``max_path`` (the engine passes ``max_path = tree depth + 1``).  At accepted depth
+    ``max_path`` the last accepted token has no slot: ``tokens[max_path - 1]`` is left unwritten
+    by the kernel and by ``tree_verify_ref`` alike."""
     if _native(parent):
         B = parent.shape[0]
         acc = torch.empty(B, dtype=torch.int32, device=parent.device)

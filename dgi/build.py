@@ -21,6 +21,10 @@ BUILD = os.path.join(HERE, "..", "build", "dgi_obj")
 OUT = os.path.join(HERE, "_C.so")
 ARCH = os.environ.get("DGI_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# extra hipcc flags per kernel file (every csrc/*.hip is built; this only adds to its line).
+# skinny_gemm_int4.hip folds groups with scalar fp32 fmas: keep the compiler from pairing them
+# into packed fp32 instructions.
+KERNEL_FLAGS = {"skinny_gemm_int4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _torch_paths():
@@ -60,7 +64,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
         obj = os.path.join(BUILD, k + ".o")
         objs.append(obj)
         if force or _newer([src] + hdrs, obj):
-            jobs.append([HIPCC, f"--offload-arch={ARCH}", *common, "-munsafe-fp-atomics", "-c", src, "-o", obj])
+            jobs.append([HIPCC, f"--offload-arch={ARCH}", *common, "-munsafe-fp-atomics", *KERNEL_FLAGS.get(k, []),
+                         "-c", src, "-o", obj])
     bsrc = os.path.join(CSRC, "bindings.cpp")
     bobj = os.path.join(BUILD, "bindings.o")
     objs.append(bobj)

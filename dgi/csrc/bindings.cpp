@@ -42,6 +42,9 @@ int dgi_dequant_fp8(const void* wq, const void* scale, void* out, int N, int K, 
 int dgi_skinny_gemm_w4(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
                        int ldy, int M, int N, int K, int cfg, hipStream_t s);
 int dgi_dequant_mxfp4(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
+int dgi_skinny_gemm_i4(const void* x, int ldx, const void* w, const void* sz, const void* bias, void* y,
+                       int ldy, int M, int N, int K, int cfg, hipStream_t s);
+int dgi_dequant_int4(const void* wq, const void* sz, void* out, int N, int K, hipStream_t s);
 int dgi_quant_rows_fp8(const void* x, int ldx, void* q, void* sx, int M, int K, hipStream_t s);
 int dgi_mfma_gemm_fp8(const void* xq, const void* sx, const void* wq, const void* sw, const void* bias, void* y,
                       int ldy, int M, int N, int K, hipStream_t s);
@@ -531,6 +534,44 @@ void dequant_mxfp4(at::Tensor out, const at::Tensor& q, const at::Tensor& scale)
            "dequant_mxfp4");
 }
 
+// q [N, K/8] and sz [N, K/128] int32 of an INT4 weight (skinny_gemm_int4.hip documents the layout), K % 128 == 0
+static int64_t check_int4(const char* name, const at::Tensor& q, const at::Tensor& sz) {
+  check_dev(q, "q"); check_dev(sz, "sz");
+  TORCH_CHECK(q.scalar_type() == at::kInt && sz.scalar_type() == at::kInt, name, ": q and sz must be int32");
+  TORCH_CHECK(q.dim() == 2 && sz.dim() == 2 && q.is_contiguous() && sz.is_contiguous(), name,
+              ": q and sz row-major 2-D");
+  TORCH_CHECK(q.device() == sz.device(), name, ": operands on one device");
+  const int64_t N = q.size(0), K = 8 * q.size(1);
+  TORCH_CHECK(K % 128 == 0 && sz.size(0) == N && sz.size(1) * 128 == K && N < (1LL << 31) && K < (1LL << 31), name,
+              ": q [N, K/8] with K%128, sz [N, K/128]");
+  TORCH_CHECK((uintptr_t)q.data_ptr() % 16 == 0 && (uintptr_t)sz.data_ptr() % 8 == 0, name,
+              ": q 16-byte aligned, sz 8-byte aligned");
+  return K;
+}
+
+// W4A16 decode GEMM over INT4 weights with a per-group fp16 scale and zero point (G = 128): out = x w^T (+ bias)
+void skinny_gemm_i4(at::Tensor out, const at::Tensor& x, const at::Tensor& q, const at::Tensor& sz,
+                    const c10::optional<at::Tensor>& bias, int64_t cfg) {
+  const int64_t N = q.size(0), K = check_int4("skinny_gemm_i4", q, sz);
+  TORCH_CHECK(q.device() == x.device(), "skinny_gemm_i4: operands on one device");
+  const void* b = check_skinny_operands("skinny_gemm_i4", out, x, N, K, bias);
+  check_rc(dgi_skinny_gemm_i4(x.data_ptr(), (int)x.stride(0), q.data_ptr(), sz.data_ptr(), b, out.data_ptr(),
+                              (int)out.stride(0), (int)x.size(0), (int)N, (int)K, (int)cfg, cur_stream()),
+           "skinny_gemm_i4");
+}
+
+// out [N, K] bf16 = bf16(float(code - zero) * float(scale)) (the route of every shape skinny_gemm_i4 does not take)
+void dequant_int4(at::Tensor out, const at::Tensor& q, const at::Tensor& sz) {
+  check_bf16(out, "out");
+  const int64_t K = check_int4("dequant_int4", q, sz);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == q.size(0) && out.size(1) == K && out.is_contiguous(),
+              "dequant_int4: out is a contiguous [N, K]");
+  TORCH_CHECK(out.device() == q.device() && (uintptr_t)out.data_ptr() % 16 == 0,
+              "dequant_int4: out on q's device, 16-byte aligned");
+  check_rc(dgi_dequant_int4(q.data_ptr(), sz.data_ptr(), out.data_ptr(), (int)q.size(0), (int)K, cur_stream()),
+           "dequant_int4");
+}
+
 // W8A8 row quantiser: q [M, K] e4m3 and sx [M] fp32 from x [M, K] bf16 (rows may be strided):
 // sx = max|x[m]| / 448 (1 for a zero row), q = rne_e4m3(x * (448 / max|x[m]|)).
 void quant_rows_fp8(at::Tensor q, at::Tensor sx, const at::Tensor& x) {
@@ -983,6 +1024,8 @@ TORCH_LIBRARY(dgi, m) {
   m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
   m.def("skinny_gemm_w4(Tensor(a!) out, Tensor x, Tensor q, Tensor scale, Tensor? bias, int cfg=0) -> ()");
   m.def("dequant_mxfp4(Tensor(a!) out, Tensor q, Tensor scale) -> ()");
+  m.def("skinny_gemm_i4(Tensor(a!) out, Tensor x, Tensor q, Tensor sz, Tensor? bias, int cfg=0) -> ()");
+  m.def("dequant_int4(Tensor(a!) out, Tensor q, Tensor sz) -> ()");
   m.def("quant_rows_fp8(Tensor(a!) q, Tensor(b!) sx, Tensor x) -> ()");
   m.def("mfma_gemm_fp8(Tensor(a!) out, Tensor xq, Tensor sx, Tensor wq, Tensor sw, Tensor? bias) -> ()");
   m.def("mfma_gemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, int sched=3, int streamk=0, int phases=0, "
@@ -1029,6 +1072,8 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("dequant_fp8", &dequant_fp8);
   m.impl("skinny_gemm_w4", &skinny_gemm_w4);
   m.impl("dequant_mxfp4", &dequant_mxfp4);
+  m.impl("skinny_gemm_i4", &skinny_gemm_i4);
+  m.impl("dequant_int4", &dequant_int4);
   m.impl("quant_rows_fp8", &quant_rows_fp8);
   m.impl("mfma_gemm_fp8", &mfma_gemm_fp8);
   m.impl("mfma_gemm", &mfma_gemm);

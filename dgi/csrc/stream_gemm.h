@@ -1,6 +1,6 @@
 // dgi/csrc/stream_gemm.h — the K-split register-ring core of the weight-streaming GEMMs
-// (skinny_gemm.hip, skinny_gemm_fp8.hip, skinny_gemm_mxfp4.hip, and moe_gemm / moe_gemm_w8 in
-// moe.hip: the grouped kernel over Bf16W and over E4m3W).
+// (skinny_gemm.hip, skinny_gemm_fp8.hip, skinny_gemm_mxfp4.hip, skinny_gemm_int4.hip, and
+// moe_gemm / moe_gemm_w8 in moe.hip: the grouped kernel over Bf16W and over E4m3W).
 //
 // Y[M, N] = X[M, K] · W[N, K]^T for decode-sized M.  At these sizes every projection is a read
 // of its weight matrix: the FLOPs are free and the kernel's job is to keep HBM3E streaming.
@@ -28,6 +28,14 @@
 // Every accumulator sees its MFMAs in K-step order, fragments ascending within a step, and the
 // partial tiles are added in wave order: results do not depend on MT, the tile count or D.
 //
+// A format whose scale is no power of two cannot put it into the B operand without rounding the
+// weight.  Such a format sets kGroupFrags > 0 (Int4W: 4 fragments = one 128-element quantisation
+// group): its fragments then take the natural K order (fragment q covers 32 contiguous elements,
+// so an MFMA never mixes two groups), each run of kGroupFrags fragments is multiplied into a
+// group accumulator of its own, next to the group's row sums of X (the same fragments against a
+// B operand of ones, once for all weight tiles), and Format::fold adds the group to the tile's
+// accumulator in fp32.  kGroupFrags = 0 is the plain path, unchanged.
+//
 // Not here: fused_decode.hip.  Its three kernels interleave the norm prologue and a persistent
 // tile cursor with the ring; sharing that is a different job.
 #pragma once
@@ -46,7 +54,7 @@ struct WFrag32 {
 struct NoScales {};
 
 struct Bf16W {
-  static constexpr int kStep = 64, kXFrags = 2;
+  static constexpr int kStep = 64, kXFrags = 2, kGroupFrags = 0;
   using Mat = const uint16_t*;
   using Ptr = const uint16_t*;
   using WFrag = WFrag32;
@@ -66,7 +74,7 @@ struct Bf16W {
 // OCP e4m3, widened in registers: every finite e4m3 value is exact in bf16.  Fragment q of lane
 // group g holds k = 128·step + 32g + 8q + j.
 struct E4m3W {
-  static constexpr int kStep = 128, kXFrags = 4;
+  static constexpr int kStep = 128, kXFrags = 4, kGroupFrags = 0;
   using Mat = const uint8_t*;
   using Ptr = const uint8_t*;
   using WFrag = WFrag32;
@@ -104,7 +112,7 @@ __device__ __forceinline__ float e8m0_to_f32(uint32_t code) { return __uint_as_f
 // (0..7) of lane group g holds k = 256·step + 64g + 8q + j: one dword of codes, decoded by four
 // v_cvt_scalef32_pk_bf16_fp4 (op_sel picks the byte, low nibble first) with the block's scale.
 struct Mxfp4W {
-  static constexpr int kStep = 256, kXFrags = 8;
+  static constexpr int kStep = 256, kXFrags = 8, kGroupFrags = 0;
   struct Mat {
     const uint8_t* q;
     const uint8_t* s;
@@ -140,6 +148,66 @@ struct Mxfp4W {
   }
 };
 
+// INT4 codes with an fp16 scale and a 4-bit zero point per 128 elements of a row (G = 128):
+// w[n, k] = (code - zero[n, k / 128]) * scale[n, k / 128].  The layout is this kernel's own, made
+// by the loader (dgi/ops/int4.py): q [N, K/8] dwords of 8 codes and sz [N, K/128] dwords of one
+// group's scale and zero point.
+//   q   Group h of a row is 16 dwords; dword 4g + c of it holds k = 128h + 32c + 8g + j, j = 0..7,
+//       element j in nibble (j >> 1) + 4 (j & 1).  Lane group g reads 16 bytes of each of the
+//       step's two groups: together the 128-byte line, and fragment q = 4h + c is one dword whose
+//       8 codes lie in a single quantisation group, in the MFMA's natural K order.
+//   sz  low half: the scale's fp16 bits; high half: 0x4300 + zero, the bf16 bits of 128 + zero.
+// (dword >> 4p) & 0x000F000F | 0x43004300 is the bf16 pair (128 + code[2p], 128 + code[2p+1]),
+// exactly: the B operand costs two bit operations per pair and no conversion.  The core's
+// grouped path then gives ag = sum x (128 + code) and xs = sum x per group, and fold adds
+// scale * (ag - (128 + zero) * xs) = scale * sum x (code - zero) in fp32: the weight is never
+// rounded.  Both fmas are explicit, so every instantiation rounds alike.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+struct Int4W {
+  static constexpr int kStep = 256, kXFrags = 8, kGroupFrags = 4;
+  struct Mat {
+    const uint32_t* q;
+    const uint32_t* sz;
+  };
+  using Ptr = Mat;
+  struct WFrag {
+    u32x4 v[2];
+    u32x2 sz;
+  };
+  // a step is 32 dwords of codes and 2 dwords of scale / zero per row
+  static __device__ __forceinline__ Ptr ptr(Mat W, size_t row, int K, int g, int w) {
+    return Ptr{W.q + row * (K >> 3) + g * 4 + (size_t)w * 32, W.sz + row * (K >> 7) + (size_t)w * 2};
+  }
+  static __device__ __forceinline__ Ptr rows(Ptr p, size_t n, int K) {
+    return Ptr{p.q + n * (K >> 3), p.sz + n * (K >> 7)};
+  }
+  static __device__ __forceinline__ void load(WFrag& f, Ptr p, size_t step) {
+    const u32x4* q = reinterpret_cast<const u32x4*>(p.q + step * 32);
+    f.v[0] = __builtin_nontemporal_load(q);
+    f.v[1] = __builtin_nontemporal_load(q + 4);
+    f.sz = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p.sz + step * 2));
+  }
+  static __device__ __forceinline__ bf16x8 ones() {
+    return as_bf16x8(u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
+  }
+  static __device__ __forceinline__ bf16x8 b_operand(const WFrag& f, NoScales, int q) {
+    const uint32_t c = f.v[q >> 2][q & 3];
+    u32x4 r;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) r[p] = ((c >> (4 * p)) & 0x000f000fu) | 0x43004300u;
+    return as_bf16x8(r);
+  }
+  static __device__ __forceinline__ f32x4 fold(f32x4 acc, f32x4 ag, f32x4 xs, const WFrag& f, int h) {
+    const uint32_t w = f.sz[h];
+    const float sc = (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
+    const float nz = -__uint_as_float(w & 0xffff0000u);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(sc, __builtin_fmaf(nz, xs[i], ag[i]), acc[i]);
+    return acc;
+  }
+};
+
 // Fragments of U K-steps: W for WT weight tiles, X for MT row tiles.
 template <class F, int MT, int WT, int U>
 struct StreamFrag {
@@ -163,6 +231,7 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
   const int r = lane & 15;
   const int g = lane >> 4;
   const int ngroups = (K >> __builtin_ctz(F::kStep)) / (NW * U);
+  constexpr bool kGrouped = F::kGroupFrags > 0;
   typename F::Ptr wrow[WT];
 #pragma unroll
   for (int t = 0; t < WT; ++t) wrow[t] = wptr_of(t, r, g, w);
@@ -172,7 +241,9 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
   for (int mt = 0; mt < MT; ++mt) {
     const int row = xrow_of(mt * 16 + r);
     xval[mt] = row >= 0;
-    xrow[mt] = X + (size_t)(xval[mt] ? row : 0) * ldx + g * (F::kStep / 4) + w * F::kStep;
+    // lane group g: a quarter of the step (fragments 8 elements apart), or, for a grouped format,
+    // its 8 elements of every 32 (fragments 32 apart: the MFMA's own A layout)
+    xrow[mt] = X + (size_t)(xval[mt] ? row : 0) * ldx + g * (kGrouped ? 8 : F::kStep / 4) + w * F::kStep;
   }
   f32x4 acc[MT][WT];
 #pragma unroll
@@ -192,7 +263,7 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
         if (xval[mt]) {
           const u32x4* p = reinterpret_cast<const u32x4*>(xrow[mt] + step * F::kStep);
 #pragma unroll
-          for (int q = 0; q < F::kXFrags; ++q) f.x[u][mt][q] = p[q];
+          for (int q = 0; q < F::kXFrags; ++q) f.x[u][mt][q] = p[kGrouped ? 4 * q : q];
         } else {  // rows that do not exist read nothing
 #pragma unroll
           for (int q = 0; q < F::kXFrags; ++q) f.x[u][mt][q] = u32x4{0u, 0u, 0u, 0u};
@@ -201,19 +272,53 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
     }
   };
   auto compute = [&](const Frag& f) {
+    if constexpr (kGrouped) {
+      constexpr int GF = F::kGroupFrags;
 #pragma unroll
-    for (int u = 0; u < U; ++u)
+      for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int t = 0; t < WT; ++t) {
-        const auto sc = F::scales(f.w[u][t]);
+        for (int h = 0; h < F::kXFrags / GF; ++h) {
+          // the group's row sums of X: every column of X · 1 is the sum, so the lane holds rows
+          // 4g .. 4g + 3 of it next to the same rows of its accumulators
+          f32x4 xs[MT];
 #pragma unroll
-        for (int q = 0; q < F::kXFrags; ++q) {
-          const bf16x8 b = F::b_operand(f.w[u][t], sc, q);
+          for (int mt = 0; mt < MT; ++mt) {
+            xs[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-            acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[u][mt][q]), b, acc[mt][t], 0, 0, 0);
+            for (int q = h * GF; q < (h + 1) * GF; ++q)
+              xs[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[u][mt][q]), F::ones(), xs[mt], 0, 0, 0);
+          }
+#pragma unroll
+          for (int t = 0; t < WT; ++t) {
+            f32x4 ag[MT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) ag[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int q = h * GF; q < (h + 1) * GF; ++q) {
+              const bf16x8 b = F::b_operand(f.w[u][t], NoScales{}, q);
+#pragma unroll
+              for (int mt = 0; mt < MT; ++mt)
+                ag[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[u][mt][q]), b, ag[mt], 0, 0, 0);
+            }
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) acc[mt][t] = F::fold(acc[mt][t], ag[mt], xs[mt], f.w[u][t], h);
+          }
         }
-      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int t = 0; t < WT; ++t) {
+          const auto sc = F::scales(f.w[u][t]);
+#pragma unroll
+          for (int q = 0; q < F::kXFrags; ++q) {
+            const bf16x8 b = F::b_operand(f.w[u][t], sc, q);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+              acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[u][mt][q]), b, acc[mt][t], 0, 0, 0);
+          }
+        }
+    }
   };
   // register ring of D groups: D - 1 in flight ahead of the one being multiplied
   Frag ring[D];

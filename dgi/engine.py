@@ -26,6 +26,9 @@ from dgi.utils.trace import phase
 
 
 WEIGHT_QUANT_MODES = (None, "fp8", "mxfp4")
+# the reference's name for a 4-bit model, accepted next to the modes above: the projections become ops.Int4Weight
+# (``LlamaModel.weight_quant == "int4"``), read from an AWQ checkpoint or rounded to nearest from bf16 weights
+WEIGHT_QUANT_AWQ = "awq"
 ACT_QUANT_MODES = (None, "fp8")       # "fp8": W8A8 on top of weight_quant="fp8"
 EXPERT_QUANT_MODES = (None, "fp8")    # FP8 weight-only experts of a MoE model (``LlamaModel.quantize_experts``)
 KV_DTYPES = (None, "fp8")      # None: KV pages in the activation dtype; "fp8": e4m3 codes + per-head scales
@@ -83,7 +86,9 @@ class EngineConfig:
     decode_lookahead: bool = True      # pure-decode graph steps: launch step N+1 before step N's
                                        # tokens are back (``LLMEngine._lookahead``); DGI_DECODE_LOOKAHEAD=0
     weight_quant: Optional[str] = None   # weight-only projections (``LlamaModel.quantize_weights``): "fp8" (e4m3,
-                                         # per-channel scales) or "mxfp4" (e2m1, one e8m0 scale per 32 elements)
+                                         # per-channel scales), "mxfp4" (e2m1, one e8m0 scale per 32 elements)
+                                         # or "awq" (the int4 format: 4-bit codes, fp16 scale and zero point per 128
+                                         # elements; rounded to nearest unless the checkpoint is an AWQ one)
     act_quant: Optional[str] = None      # "fp8" (with weight_quant="fp8"): W8A8 — per-token e4m3 activations and the
                                          # e4m3 GEMM for steps of >= ops.W8A8_MIN_M rows (a token's numerics then
                                          # depend on its step's row count)
@@ -95,9 +100,9 @@ class EngineConfig:
         if self.kv_dtype not in KV_DTYPES:
             raise ValueError(f"EngineConfig.kv_dtype={self.kv_dtype!r}: supported values are "
                              f"{', '.join(repr(m) for m in KV_DTYPES)}")
-        if self.weight_quant not in WEIGHT_QUANT_MODES:
+        if self.weight_quant not in WEIGHT_QUANT_MODES + (WEIGHT_QUANT_AWQ,):
             raise ValueError(f"EngineConfig.weight_quant={self.weight_quant!r}: supported values are "
-                             f"{', '.join(repr(m) for m in WEIGHT_QUANT_MODES)}")
+                             f"{', '.join(repr(m) for m in WEIGHT_QUANT_MODES + (WEIGHT_QUANT_AWQ,))}")
         if self.act_quant not in ACT_QUANT_MODES:
             raise ValueError(f"EngineConfig.act_quant={self.act_quant!r}: supported values are "
                              f"{', '.join(repr(m) for m in ACT_QUANT_MODES)}")

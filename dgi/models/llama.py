@@ -100,6 +100,9 @@ class LlamaLayerWeights:
 
 
 QUANT_SLOTS = ("qkv", "o", "gate_up", "down")    # the projections quantize_weights replaces
+# quantize_weights mode -> (container, quantiser of a bf16 [N, K] weight)
+QUANT_KINDS = {"fp8": (ops.Fp8Weight, ops.quantize_fp8), "mxfp4": (ops.Mxfp4Weight, ops.quantize_mxfp4),
+               "int4": (ops.Int4Weight, ops.quantize_int4)}
 EXPERT_SLOTS = ("experts_gate_up", "experts_down")    # the tensors quantize_experts replaces
 
 
@@ -152,7 +155,8 @@ class LlamaModel:
         self.norms_folded = False    # fold_norms ran: in_norm / post_norm are ones, qkv / gate_up carry the gains
         self.fold_impl = None        # rows -> run the fused-norm layers? (dgi.runtime.gemm_pad)
         self._ss_buf: Optional[torch.Tensor] = None
-        # "fp8" / "mxfp4": the four projections per layer are ops.Fp8Weight / ops.Mxfp4Weight
+        # "fp8" / "mxfp4" / "int4": the four projections per layer are ops.Fp8Weight / ops.Mxfp4Weight /
+        # ops.Int4Weight
         self.weight_quant: Optional[str] = None
         self.act_quant: Optional[str] = None        # "fp8": W8A8 above ops.W8A8_MIN_M rows (quantize_weights)
         self._quant_scratch: Optional[torch.Tensor] = None
@@ -282,14 +286,18 @@ class LlamaModel:
         """Weight-only quantisation of each layer's qkv / o / gate_up / down projection, one layer
         at a time, dropping the bf16 tensor as it goes: ``"fp8"`` (``ops.quantize_fp8``: e4m3 codes,
         one fp32 scale per output channel) or ``"mxfp4"`` (``ops.quantize_mxfp4``: e2m1 codes, one
-        e8m0 scale per 32 elements).  Norm gains (``q_norm`` / ``k_norm`` included), ``qkv_bias``,
-        ``embed`` and ``lm_head`` keep their dtype.  Steps then run ``_forward_layers_quant``.
+        e8m0 scale per 32 elements) or ``"int4"`` (``ops.quantize_int4``: 4-bit codes, one fp16 scale and
+        one zero point per 128 elements; an AWQ checkpoint loads into this mode, and ``"awq"``, the name
+        of the public switches, means the same).  Norm gains (``q_norm`` / ``k_norm`` included),
+        ``qkv_bias``, ``embed`` and ``lm_head`` keep their dtype.  Steps then run ``_forward_layers_quant``.
 
         ``act_quant="fp8"`` (W8A8, fp8 weights only) marks every quantised projection so that steps
         of at least ``ops.W8A8_MIN_M`` rows quantise their activations per token and run the e4m3
         GEMM (``ops.linear_w8a8``); smaller steps stay W8A16."""
-        if mode not in ("fp8", "mxfp4"):
-            raise ValueError(f"quantize_weights: unsupported mode {mode!r} (supported: 'fp8', 'mxfp4')")
+        if mode == "awq":       # EngineConfig.weight_quant's name for the int4 format
+            mode = "int4"
+        if mode not in QUANT_KINDS:
+            raise ValueError(f"quantize_weights: unsupported mode {mode!r} (supported: 'fp8', 'mxfp4', 'int4')")
         if act_quant not in (None, "fp8"):
             raise ValueError(f"quantize_weights: unsupported act_quant {act_quant!r} (supported: None, 'fp8')")
         if self.cfg.is_moe:
@@ -304,7 +312,17 @@ class LlamaModel:
         if self.weight_quant:
             raise RuntimeError(f"quantize_weights: the model's weights are {self.weight_quant}-quantised already; "
                                f"quantise a model holding the bf16 weights to {mode!r}")
-        kind, quantise = (ops.Fp8Weight, ops.quantize_fp8) if mode == "fp8" else (ops.Mxfp4Weight, ops.quantize_mxfp4)
+        kind, quantise = QUANT_KINDS[mode]
+        self._adopt_quantised(mode, kind, quantise)
+        self._set_act_quant(act_quant)
+        if self.device.type == "cuda":
+            # the KV budget reads driver-free memory: hand the freed bf16 blocks back to the driver
+            torch.cuda.empty_cache()
+        return self
+
+    def _adopt_quantised(self, mode: str, kind, quantise=None) -> None:
+        """Quantise the projections that are not ``kind`` yet (a loader may have put them there),
+        share the dequantisation scratch among them and mark the model ``mode``-quantised."""
         largest = 0
         for L in self.layers:
             for k in QUANT_SLOTS:
@@ -322,14 +340,9 @@ class LlamaModel:
                 for k in QUANT_SLOTS:
                     getattr(L, k).scratch = self._quant_scratch
         self.weight_quant = mode
-        self._set_act_quant(act_quant)
-        if self.device.type == "cuda":
-            # the KV budget reads driver-free memory: hand the freed bf16 blocks back to the driver
-            torch.cuda.empty_cache()
-        return self
 
     def _set_act_quant(self, act_quant: Optional[str]) -> None:
-        if self.weight_quant == "fp8":      # mxfp4 weights have no activation mode (quantize_weights refuses one)
+        if self.weight_quant == "fp8":      # mxfp4 and int4 weights have no activation mode (quantize_weights refuses one)
             for L in self.layers:
                 for k in QUANT_SLOTS:
                     getattr(L, k).act = act_quant
@@ -429,11 +442,15 @@ class LlamaModel:
 
     def tensors(self):
         """(name, tensor) pairs of every weight (lm_head omitted when tied).  A quantised
-        projection yields its codes and its scales as ``<name>.q`` and ``<name>.scale``."""
+        projection yields its codes and its scales as ``<name>.q`` and ``<name>.scale`` (int4: ``<name>.sz``,
+        scale and zero point in one word)."""
         for i, L in enumerate(self.layers):
             for k in LlamaLayerWeights.__slots__:
                 t = getattr(L, k)
-                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
+                if isinstance(t, ops.Int4Weight):
+                    yield f"layers.{self.layer_start + i}.{k}.q", t.q
+                    yield f"layers.{self.layer_start + i}.{k}.sz", t.sz
+                elif isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
                     yield f"layers.{self.layer_start + i}.{k}.q", t.q
                     yield f"layers.{self.layer_start + i}.{k}.scale", t.scale
                 elif t is not None:
@@ -469,8 +486,9 @@ class LlamaModel:
         for L in self.layers:
             for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias, L.q_norm, L.k_norm,
                       L.router, L.experts_gate_up, L.experts_down):
-                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
-                    n += t.nbytes()      # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements)
+                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Int4Weight, ops.Fp8ExpertWeight)):
+                    # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements; int4: 4 bytes per 128)
+                    n += t.nbytes()
                 elif t is not None:
                     n += t.numel() * t.element_size()
         for t in (self.embed, self.norm):

@@ -131,13 +131,65 @@ def load_kv_scales(rd, layer_start: int, layer_end: int, num_kv_heads: int) -> O
     return out
 
 
+AWQ_SUPPORTED = "quant_method 'awq' with bits 4, group_size 128, zero_point true and version 'gemm'"
+
+
+def checkpoint_quantization(path: str) -> Optional[str]:
+    """``"int4"`` for a checkpoint whose ``config.json`` declares the one pre-quantised format that is
+    read (``AWQ_SUPPORTED``), None for one without ``quantization_config``; every other declared
+    format — other methods (all of GPTQ), bit widths, group sizes, versions — is a ValueError."""
+    cfg = os.path.join(path, "config.json")
+    if not os.path.exists(cfg):
+        return None
+    with open(cfg) as f:
+        qc = json.load(f).get("quantization_config")
+    if not qc:
+        return None
+    ok = (str(qc.get("quant_method", "")).lower() == "awq" and qc.get("bits") == 4 and qc.get("group_size") == 128
+          and qc.get("zero_point") is True and str(qc.get("version", "")).lower() == "gemm")
+    if not ok:
+        shown = {k: qc.get(k) for k in ("quant_method", "bits", "group_size", "zero_point", "version")}
+        raise ValueError(f"{path}: unsupported quantization_config {shown}; the only pre-quantised checkpoints "
+                         f"read are {AWQ_SUPPORTED}")
+    return "int4"
+
+
+def _read_awq(rd: CheckpointReader, names, slot, device):
+    """The ``Int4Weight`` of the AWQ linear layers ``names`` (without suffix), concatenated along N, for
+    a model slot of that shape: each ``qweight`` / ``qzeros`` / ``scales`` triple is repacked into the
+    kernel's layout on the CPU, then moved."""
+    from dgi import ops
+    parts = []
+    for name in names:
+        for suffix in ("qweight", "qzeros", "scales"):
+            if f"{name}.{suffix}" not in rd:
+                raise KeyError(f"{rd.path}: AWQ checkpoint without {name}.{suffix}")
+        parts.append(ops.int4_from_awq(rd.read(name + ".qweight"), rd.read(name + ".qzeros"), rd.read(name + ".scales")))
+    w = ops.int4_cat(parts)
+    if tuple(w.shape) != tuple(slot.shape):
+        raise ValueError(f"checkpoint tensors {list(names)} give shape {tuple(w.shape)} != model slot {tuple(slot.shape)}")
+    return ops.Int4Weight(w.q.to(device), w.sz.to(device))
+
+
 def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
     """Fill a ``LlamaModel`` (created with ``init="empty"``) from an HF checkpoint.
 
     ``model.cfg`` is the LOCAL config (per-rank heads / intermediate for TP);
-    ``full`` is the checkpoint's.  Returns {"tensors": n, "bytes": b}."""
+    ``full`` is the checkpoint's.  Returns {"tensors": n, "bytes": b}.
+
+    An AWQ checkpoint (``checkpoint_quantization``) fills the four projections of each layer with
+    ``ops.Int4Weight`` repacked from ``*.qweight`` / ``*.qzeros`` / ``*.scales`` and leaves the model
+    with ``weight_quant == "int4"``; everything else in it is read as usual.  Pipeline stages read
+    their layers; tensor parallelism would slice inside packed words and quantisation groups and
+    is refused."""
     if hasattr(model, "_check_not_quantised"):     # the loader writes the bf16 tensors in place
         model._check_not_quantised("load_checkpoint")
+    awq = checkpoint_quantization(path) == "int4"
+    if awq and tp > 1:
+        raise ValueError(f"{path}: tensor parallelism over an AWQ checkpoint is not supported (tp={tp}); "
+                         "serve it on one GPU or over pipeline stages")
+    if awq and model.cfg.is_moe:
+        raise ValueError(f"{path}: AWQ checkpoints of MoE models are not supported")
     model.norms_folded = False
     rd = CheckpointReader(path)
     c = model.cfg
@@ -153,9 +205,12 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
         L = model.layers[i]
         p = f"model.layers.{li}."
         a = p + "self_attn."
-        _put(L.qkv[:ql], rd.read(a + "q_proj.weight", rows=q_rows))
-        _put(L.qkv[ql:ql + kl], rd.read(a + "k_proj.weight", rows=kv_rows))
-        _put(L.qkv[ql + kl:], rd.read(a + "v_proj.weight", rows=kv_rows))
+        if awq:
+            L.qkv = _read_awq(rd, [a + "q_proj", a + "k_proj", a + "v_proj"], L.qkv, model.device)
+        else:
+            _put(L.qkv[:ql], rd.read(a + "q_proj.weight", rows=q_rows))
+            _put(L.qkv[ql:ql + kl], rd.read(a + "k_proj.weight", rows=kv_rows))
+            _put(L.qkv[ql + kl:], rd.read(a + "v_proj.weight", rows=kv_rows))
         n += 3
         if L.qkv_bias is not None:
             _put(L.qkv_bias[:ql], rd.read(a + "q_proj.bias", rows=q_rows))
@@ -169,9 +224,15 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
                     raise KeyError(f"{path}: {model.cfg.arch} checkpoint without {name}")
                 _put(slot, rd.read(name))
             n += 2
-        _put(L.o, rd.read(a + "o_proj.weight", cols=q_rows) if tp > 1 else rd.read(a + "o_proj.weight"))
+        if awq:
+            L.o = _read_awq(rd, [a + "o_proj"], L.o, model.device)
+        else:
+            _put(L.o, rd.read(a + "o_proj.weight", cols=q_rows) if tp > 1 else rd.read(a + "o_proj.weight"))
         m = p + "mlp."
-        if L.router is not None:
+        if awq:
+            L.gate_up = _read_awq(rd, [m + "gate_proj", m + "up_proj"], L.gate_up, model.device)
+            L.down = _read_awq(rd, [m + "down_proj"], L.down, model.device)
+        elif L.router is not None:
             # Qwen3-MoE: the published per-expert tensors, each read straight into its slice of the
             # stacked [E, 2I, H] / [E, H, I] weights (never a CPU copy of a whole layer's experts)
             Im = c.moe_intermediate_size
@@ -194,7 +255,7 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
         else:
             _put(L.gate_up[:Il], rd.read(m + "gate_proj.weight", rows=i_rows))
             _put(L.gate_up[Il:], rd.read(m + "up_proj.weight", rows=i_rows))
-        if L.router is None:
+        if L.router is None and not awq:
             _put(L.down, rd.read(m + "down_proj.weight", cols=i_rows) if tp > 1 else rd.read(m + "down_proj.weight"))
         _put(L.in_norm, rd.read(p + "input_layernorm.weight"))
         _put(L.post_norm, rd.read(p + "post_attention_layernorm.weight"))
@@ -211,6 +272,11 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
             else:   # tied checkpoint served by an untied slot (last stage without the embedding)
                 _put(model.lm_head, rd.read("model.embed_tokens.weight"))
             n += 1
+    if awq:
+        from dgi import ops
+        model._adopt_quantised("int4", ops.Int4Weight)
+        if model.device.type == "cuda":
+            torch.cuda.empty_cache()      # the empty bf16 projections the packed ones replaced
     # per-layer KV-cache scales, used only by an fp8 KV pool (``EngineConfig.kv_dtype``)
     model.kv_scales_loaded = load_kv_scales(rd, model.layer_start, model.layer_end, c.num_kv_heads)
     out = {"tensors": n, "bytes": rd.bytes_read, "path": path}

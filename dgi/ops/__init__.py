@@ -22,6 +22,7 @@ import torch
 from dgi.ops.fp8 import E4M3_MAX, Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
 from dgi.ops.fp8 import Fp8ExpertWeight, quantize_fp8_experts  # noqa: F401  (public: the MoE experts' container)
 from dgi.ops.mxfp4 import Mxfp4Weight, quantize_mxfp4  # noqa: F401  (public: ops.Mxfp4Weight, ops.quantize_mxfp4)
+from dgi.ops.int4 import Int4Weight, int4_cat, int4_from_awq, quantize_int4  # noqa: F401  (public)
 
 _LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_C.so")
 _loaded = False
@@ -810,14 +811,87 @@ def _linear_mxfp4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor],
     return r
 
 
+# INT4 weight-only projections with a per-group scale and zero point (skinny_gemm_int4.hip).  The
+# routing is mxfp4's: the W4A16 kernel takes M <= 32, K % 1024 == 0, N % 16 == 0; everything else is
+# dequantised to bf16 (dequant_int4) and runs the bf16 GEMM.  Unlike mxfp4 the two routes do not
+# multiply the same numbers: the kernel keeps (code - zero) * scale exact, the dequantised copy is
+# that product rounded to bf16 (as fp8's dequant route rounds).
+# launch configs of skinny_gemm_i4: cfg -> (waves per workgroup, column tiles per wave, 256-deep
+# K steps per load group, ring depth at M <= 16), as skinny_gemm_w4's.  Steps of more than 16 rows run
+# rings of at most two groups, one on 8 waves with more than one column tile, and cfg 8 two tiles.
+SKINNY_I4_CFGS = {1: (4, 1, 1, 4), 2: (4, 1, 1, 2), 3: (8, 1, 1, 2), 4: (8, 1, 1, 4), 5: (4, 2, 1, 2),
+                  6: (8, 2, 1, 2), 7: (4, 4, 1, 2), 8: (8, 4, 1, 2)}
+SKINNY_I4_CFG = _env_cfg("DGI_SKINNY_I4_CFG", 0, SKINNY_I4_CFGS)    # > 0 forces a launch config (sweeps)
+
+
+def skinny_i4_cfg_ok(cfg: int, N: int, K: int) -> bool:
+    """Whether launch config ``cfg`` of ``skinny_gemm_i4`` divides an [N, K] weight."""
+    return _skinny_cfg_ok(SKINNY_I4_CFGS, 2, 256, cfg, N, K)
+
+
+def _skinny_i4_cfg(M: int, N: int, K: int = 0) -> int:
+    """Launch config per row count and shape (profiles/int4_weights/README.md, weights cold,
+    hipGraph-timed).  The bytes per row and step and the X traffic per weight byte are the mxfp4
+    kernel's, and so is the table, but for the gate_up widths: two column tiles up to 4 rows (four tiles
+    cost 20 % there at N = 57344), four above, on 4 waves at every row count — cfg 8, which runs two
+    tiles and a single group on two row tiles, is 25-30 % behind cfg 7 at M = 32 and is never picked."""
+    if SKINNY_I4_CFG > 0:
+        return SKINNY_I4_CFG
+    one = 3 if (M <= 2 and K > 0 and K % 2048 == 0) else 0
+    if N < 6144 or N % 64:
+        return one
+    if N >= 16384:
+        return 5 if M <= 4 else 7
+    if 256 < N // 32 < 512:
+        return one if M <= 2 else 7
+    return 5
+
+
+def linear_int4_ref(x: torch.Tensor, w: Int4Weight, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return torch.nn.functional.linear(x.float(), w.dequant(torch.float32),
+                                      None if bias is None else bias.float()).to(x.dtype)
+
+
+def dequant_int4(w: Int4Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] copy of an int4 weight, ``bf16(float(code - zero) * float(scale))``; ``out``: a flat bf16
+    buffer of >= N*K elements."""
+    N, K = w.shape
+    if out is None or out.numel() < N * K or out.device != w.device or out.dtype != torch.bfloat16:
+        out = torch.empty(N * K, dtype=torch.bfloat16, device=w.device)
+    out = out.view(-1)[: N * K].view(N, K)
+    if w.q.is_cuda:
+        load_native(required=True)
+        _call("dequant_int4", out, w.q, w.sz)
+    else:
+        out.copy_(w.dequant(torch.bfloat16))
+    return out
+
+
+def _linear_int4(x: torch.Tensor, w: Int4Weight, bias: Optional[torch.Tensor], out: Optional[torch.Tensor]):
+    if x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16:
+        M, K = x.shape
+        N = w.shape[0]
+        if _use_skinny_quant(M, N, K) and _skinny_takes(x):
+            return _skinny_run("skinny_gemm_i4", x, N, out, w.q, w.sz, bias, _skinny_i4_cfg(M, N, K))
+        r = torch.nn.functional.linear(x, dequant_int4(w, w.scratch), bias)
+    else:
+        r = linear_int4_ref(x, w, bias)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
 def linear(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = x @ w.T (+ bias) for a 2-D activation; [N, K] weights as stored (bf16 tensor, ``Fp8Weight``
-    or ``Mxfp4Weight``)."""
+    """y = x @ w.T (+ bias) for a 2-D activation; [N, K] weights as stored (bf16 tensor, ``Fp8Weight``,
+    ``Mxfp4Weight`` or ``Int4Weight``)."""
     if isinstance(w, Fp8Weight):
         return _linear_fp8(x, w, bias, out)
     if isinstance(w, Mxfp4Weight):
         return _linear_mxfp4(x, w, bias, out)
+    if isinstance(w, Int4Weight):
+        return _linear_int4(x, w, bias, out)
     if x.dim() != 2:
         return torch.nn.functional.linear(x, w, bias)
     M, K = x.shape

@@ -401,9 +401,11 @@ def main(argv=None) -> int:
     ap.add_argument("--max-model-len", type=int, default=4096)
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--weight-quant", default=None, choices=["fp8", "mxfp4"],
-                    help="weight-only quantisation of the layer projections: fp8 (e4m3) or mxfp4 (OCP e2m1 with e8m0 "
-                         "block scales) (default: bf16 weights)")
+    ap.add_argument("--weight-quant", default=None, choices=["fp8", "mxfp4", "awq"],
+                    help="weight-only quantisation of the layer projections: fp8 (e4m3), mxfp4 (OCP e2m1 with e8m0 "
+                         "block scales) or awq (int4: 4-bit codes, an fp16 scale and a zero point per 128 elements; an AWQ "
+                         "checkpoint loads that way by itself, bf16 weights are rounded to nearest) "
+                         "(default: bf16 weights)")
     ap.add_argument("--act-quant", default=None, choices=["fp8"],
                     help="with --weight-quant fp8: W8A8, per-token e4m3 activations and the e4m3 GEMM for steps of "
                          "at least DGI_W8A8_MIN_M rows, 2048 unless set (default: bf16 activations at every step size)")

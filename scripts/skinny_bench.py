@@ -8,8 +8,9 @@ model pass ago (the 256 MB MALL cannot hold them).  Prints one JSON line per
 adds the W8A16 kernel (``skinny_gemm_w8``, e4m3 weights at half the bytes) as
 ``fp8_c<cfg>`` columns, over the same number of rotating copies; ``--w4-cfg`` the
 W4A16 kernel (``skinny_gemm_w4``, MXFP4 weights at a quarter of the bytes plus one scale
-byte per 32 elements) as ``w4_c<cfg>``.  ``-1`` in either list stands for the config the
-ops layer picks for the shape and row count.
+byte per 32 elements) as ``w4_c<cfg>``; ``--i4-cfg`` the INT4 kernel (``skinny_gemm_i4``, 4-bit codes
+plus four bytes of scale and zero point per 128 elements) as ``i4_c<cfg>``.  ``-1`` in any of the
+lists stands for the config the ops layer picks for the shape and row count.
 """
 import argparse
 import json
@@ -69,6 +70,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--fp8-cfg", type=int, nargs="*", default=[0], help="skinny_gemm_w8 launch configs (none: skip)")
     ap.add_argument("--w4-cfg", type=int, nargs="*", default=[], help="skinny_gemm_w4 launch configs (none: skip)")
+    ap.add_argument("--i4-cfg", type=int, nargs="*", default=[], help="skinny_gemm_i4 launch configs (none: skip)")
     ap.add_argument("--no-hipblaslt", action="store_true")
     ap.add_argument("--graph", action="store_true", help="time hipGraph replays instead of eager launches")
     ap.add_argument("--out", default=None)
@@ -81,6 +83,7 @@ def main():
         ws = [torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02 for _ in range(copies)]
         qs = [ops.quantize_fp8(w) for w in ws] if a.fp8_cfg else []
         q4 = [ops.quantize_mxfp4(w) for w in ws] if a.w4_cfg else []
+        i4 = [ops.quantize_int4(w) for w in ws] if a.i4_cfg else []
         for M in a.ms:
             x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
             out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
@@ -98,6 +101,11 @@ def main():
                 if ops.skinny_w4_cfg_ok(pick, N, K):
                     impls["w4_pick" if c < 0 else f"w4_c{c}"] = (lambda c_: lambda i: torch.ops.dgi.skinny_gemm_w4(
                         out, x, q4[i % copies].q, q4[i % copies].scale, None, c_))(pick)
+            for c in a.i4_cfg:
+                pick = ops._skinny_i4_cfg(M, N, K) if c < 0 else c
+                if ops.skinny_i4_cfg_ok(pick, N, K):
+                    impls["i4_pick" if c < 0 else f"i4_c{c}"] = (lambda c_: lambda i: torch.ops.dgi.skinny_gemm_i4(
+                        out, x, i4[i % copies].q, i4[i % copies].sz, None, c_))(pick)
             ref = F.linear(x.float(), ws[0].float())
             torch.ops.dgi.skinny_gemm(out, x, ws[0], None, 0)
             err = (out.float() - ref).abs().max().item()
@@ -111,20 +119,26 @@ def main():
                 err4 = (out.float() - F.linear(x.float(), q4[0].dequant())).abs().max().item()
                 # what the format costs: the quantised projection against the bf16 one, relative rms
                 rms4 = ((out.float() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
+            erri = rmsi = None
+            if a.i4_cfg:
+                torch.ops.dgi.skinny_gemm_i4(out, x, i4[0].q, i4[0].sz, None, 0)
+                erri = (out.float() - F.linear(x.float(), i4[0].dequant())).abs().max().item()
+                rmsi = ((out.float() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
             for impl, fn in impls.items():
                 us = timed(fn, a.iters, a.graph)
-                fp8, w4 = impl.startswith("fp8"), impl.startswith("w4")
-                nbytes = N * K * 2 if not (fp8 or w4) else qs[0].nbytes() if fp8 else q4[0].nbytes()
+                fp8, w4, wi = impl.startswith("fp8"), impl.startswith("w4"), impl.startswith("i4")
+                nbytes = qs[0].nbytes() if fp8 else q4[0].nbytes() if w4 else i4[0].nbytes() if wi else N * K * 2
                 rows.append({"shape": name, "M": M, "N": N, "K": K, "impl": impl, "us": round(us, 2),
                              "weight_TBs": round(nbytes / us / 1e6, 2),
-                             "max_err": round(err8 if fp8 else err4 if w4 else err, 4),
+                             "max_err": round(err8 if fp8 else err4 if w4 else erri if wi else err, 4),
                              "timing": "graph" if a.graph else "eager"})
-                if w4:
-                    rows[-1]["rel_rms_vs_bf16"] = round(rms4, 4)
+                if w4 or wi:
+                    rows[-1]["rel_rms_vs_bf16"] = round(rms4 if w4 else rmsi, 4)
                 if impl.endswith("_pick"):
-                    rows[-1]["cfg"] = ops._skinny_w8_cfg(M, N) if fp8 else ops._skinny_w4_cfg(M, N, K)
+                    rows[-1]["cfg"] = (ops._skinny_w8_cfg(M, N) if fp8 else ops._skinny_w4_cfg(M, N, K) if w4
+                                       else ops._skinny_i4_cfg(M, N, K))
                 print(json.dumps(rows[-1]), flush=True)
-        del ws, qs, q4
+        del ws, qs, q4, i4
         torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "w") as f:

@@ -15,8 +15,9 @@ Config keys accepted (SURVEY Appendix C mapping): ``model_id``, ``device``,
 ``max_running_requests``/``max_num_seqs``, ``chunked_prefill_size``,
 ``enable_prefix_caching``, ``context_length``/``max_model_len``,
 ``num_blocks``, ``use_graphs``/``enforce_eager``, ``quantization``/``weight_quant``
-(``"fp8"``: weight-only e4m3 projections, ``"mxfp4"``: weight-only OCP MXFP4 projections; anything else is served
-unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
+(``"fp8"``: weight-only e4m3 projections, ``"mxfp4"``: weight-only OCP MXFP4 projections, ``"awq"``:
+weight-only 4-bit projections with group scales and zero points, read from an AWQ checkpoint or rounded from bf16;
+anything else is served unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
 ``DGI_W8A8_MIN_M`` rows, default 2048; ``quantization: "fp8"`` alone stays W8A16), ``expert_quant`` (``"fp8"``:
 weight-only e4m3 experts of a MoE model; anything else, or a dense model, is served with bf16 experts); nested ``sglang``/``vllm``/
 ``native`` dicts are merged in.
@@ -109,11 +110,18 @@ class NativeLLMEngine(LLMBaseEngine):
         quant = c.get("weight_quant", c.get("quantization"))
         if quant is not None and str(quant).lower() in ("", "none"):
             quant = None
-        if quant is not None and str(quant).lower() not in ("fp8", "mxfp4"):
+        if quant is not None and str(quant).lower() not in ("fp8", "mxfp4", "awq"):
             logger.warning("quantization=%r is not supported by the native engine (supported: 'fp8', 'mxfp4', "
-                           "weight-only); serving %s unquantised", quant, model_id)
+                           "'awq', weight-only); serving %s unquantised", quant, model_id)
             quant = None
         quant = None if quant is None else str(quant).lower()
+        if quant == "awq":
+            # the reference's name for a 4-bit checkpoint: an AWQ checkpoint loads as int4 by itself; over
+            # bf16 weights the same format is filled by plain rounding
+            from dgi.models.weights import checkpoint_quantization
+            if ckpt is None or checkpoint_quantization(ckpt) is None:
+                logger.info("quantization='awq' over bf16 weights: %s is quantised to int4 round-to-nearest per group "
+                            "of 128, which is not AWQ's activation-aware calibration", model_id)
         # W8A8 is opt-in: quantization "fp8" alone stays weight-only (W8A16)
         actq = c.get("act_quant")
         if actq is not None and str(actq).lower() in ("", "none"):

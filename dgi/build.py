@@ -22,9 +22,10 @@ OUT = os.path.join(HERE, "_C.so")
 ARCH = os.environ.get("DGI_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # extra hipcc flags per kernel file (every csrc/*.hip is built; this only adds to its line).
-# skinny_gemm_int4.hip folds groups with scalar fp32 fmas: keep the compiler from pairing them
-# into packed fp32 instructions.
-KERNEL_FLAGS = {"skinny_gemm_int4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# skinny_gemm_int4.hip and moe_int4.hip fold groups with scalar fp32 fmas: keep the compiler from
+# pairing them into packed fp32 instructions.
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+KERNEL_FLAGS = {"skinny_gemm_int4.hip": _NO_PACKED_FP32, "moe_int4.hip": _NO_PACKED_FP32}
 
 
 def _torch_paths():

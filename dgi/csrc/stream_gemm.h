@@ -1,6 +1,7 @@
 // dgi/csrc/stream_gemm.h — the K-split register-ring core of the weight-streaming GEMMs
 // (skinny_gemm.hip, skinny_gemm_fp8.hip, skinny_gemm_mxfp4.hip, skinny_gemm_int4.hip, and
-// moe_gemm / moe_gemm_w8 in moe.hip: the grouped kernel over Bf16W and over E4m3W).
+// moe_gemm / moe_gemm_w8 in moe.hip and moe_gemm_w4 in moe_int4.hip: the grouped kernel of
+// moe_gemm.h over Bf16W, over E4m3W and over Int4GroupW).
 //
 // Y[M, N] = X[M, K] · W[N, K]^T for decode-sized M.  At these sizes every projection is a read
 // of its weight matrix: the FLOPs are free and the kernel's job is to keep HBM3E streaming.
@@ -191,20 +192,44 @@ struct Int4W {
   static __device__ __forceinline__ bf16x8 ones() {
     return as_bf16x8(u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
   }
-  static __device__ __forceinline__ bf16x8 b_operand(const WFrag& f, NoScales, int q) {
+  // WF: this format's WFrag or Int4GroupW's (v and sz index alike)
+  template <class WF>
+  static __device__ __forceinline__ bf16x8 b_operand(const WF& f, NoScales, int q) {
     const uint32_t c = f.v[q >> 2][q & 3];
     u32x4 r;
 #pragma unroll
     for (int p = 0; p < 4; ++p) r[p] = ((c >> (4 * p)) & 0x000f000fu) | 0x43004300u;
     return as_bf16x8(r);
   }
-  static __device__ __forceinline__ f32x4 fold(f32x4 acc, f32x4 ag, f32x4 xs, const WFrag& f, int h) {
+  template <class WF>
+  static __device__ __forceinline__ f32x4 fold(f32x4 acc, f32x4 ag, f32x4 xs, const WF& f, int h) {
     const uint32_t w = f.sz[h];
     const float sc = (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
     const float nz = -__uint_as_float(w & 0xffff0000u);
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(sc, __builtin_fmaf(nz, xs[i], ag[i]), acc[i]);
     return acc;
+  }
+};
+
+// Int4W's rows read one quantisation group per step: 128 deep, 64 bytes of codes and one sz dword
+// per row.  Lane group g reads the 16 contiguous bytes of dwords 4g .. 4g + 3 of group h = step
+// (fragment c = dword 4g + c, k = 128·step + 32c + 8g + j); the four lane groups of a row read the
+// same sz dword.  A K of any multiple of 256 then has an even step count, which 2 waves always
+// divide and 4 do when K % 512 == 0: the grouped expert GEMM's geometry (moe_int4.hip), whose K
+// of 768 is three of Int4W's steps.  The operand and the fold are Int4W's.
+struct Int4GroupW : Int4W {
+  static constexpr int kStep = 128, kXFrags = 4, kGroupFrags = 4;
+  struct WFrag {
+    u32x4 v[1];
+    uint32_t sz[1];
+  };
+  static __device__ __forceinline__ Ptr ptr(Mat W, size_t row, int K, int g, int w) {
+    return Ptr{W.q + row * (K >> 3) + g * 4 + (size_t)w * 16, W.sz + row * (K >> 7) + (size_t)w};
+  }
+  static __device__ __forceinline__ void load(WFrag& f, Ptr p, size_t step) {
+    f.v[0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p.q + step * 16));
+    f.sz[0] = __builtin_nontemporal_load(p.sz + step);
   }
 };
 

@@ -18,7 +18,7 @@ import torch
 
 from dgi.kv.block_pool import BlockPool, OutOfBlocks, num_blocks_for_budget
 from dgi.models.config import ModelConfig, get_config
-from dgi.models.llama import LlamaModel
+from dgi.models.llama import EXPERT_QUANT_KINDS, LlamaModel
 from dgi.runtime.model_runner import ModelRunner
 from dgi.sched.request import Request, SamplingParams, Status
 from dgi.sched.scheduler import Scheduler, SchedulerConfig
@@ -30,7 +30,9 @@ WEIGHT_QUANT_MODES = (None, "fp8", "mxfp4")
 # (``LlamaModel.weight_quant == "int4"``), read from an AWQ checkpoint or rounded to nearest from bf16 weights
 WEIGHT_QUANT_AWQ = "awq"
 ACT_QUANT_MODES = (None, "fp8")       # "fp8": W8A8 on top of weight_quant="fp8"
-EXPERT_QUANT_MODES = (None, "fp8")    # FP8 weight-only experts of a MoE model (``LlamaModel.quantize_experts``)
+# weight-only experts of a MoE model (``LlamaModel.quantize_experts``): "fp8" (e4m3), or "awq", the public name
+# of the int4 format as for weight_quant (``LlamaModel.expert_quant == "int4"``, rounded to nearest from bf16)
+EXPERT_QUANT_MODES = (None, "fp8", "awq")
 KV_DTYPES = (None, "fp8")      # None: KV pages in the activation dtype; "fp8": e4m3 codes + per-head scales
 logger = logging.getLogger(__name__)
 
@@ -44,7 +46,7 @@ def refuse_fp8_kv(cfg, what: str) -> None:
 
 
 def refuse_expert_quant(cfg, what: str) -> None:
-    """FP8 experts are served by the single-GPU engine only, as MoE models themselves are measured;
+    """Quantised experts are served by the single-GPU engine only, as MoE models themselves are measured;
     the multi-rank layouts refuse the knob at configuration time (``what`` names the layout)."""
     if getattr(cfg, "expert_quant", None):
         raise ValueError(f"expert_quant={cfg.expert_quant!r} is not supported with {what}: serve it from a "
@@ -94,7 +96,9 @@ class EngineConfig:
                                          # depend on its step's row count)
     kv_dtype: Optional[str] = None       # "fp8": e4m3 KV pages with per-head scales (``BlockPool.kv_scale``)
     expert_quant: Optional[str] = None   # MoE models: "fp8" — weight-only e4m3 experts with per-expert, per-channel
-                                         # scales (``LlamaModel.quantize_experts``); everything else stays bf16
+                                         # scales — or "awq" — weight-only 4-bit experts, an fp16 scale and a zero
+                                         # point per 128 elements, rounded to nearest from the bf16 weights
+                                         # (``LlamaModel.quantize_experts``); everything else stays bf16
 
     def __post_init__(self):
         if self.kv_dtype not in KV_DTYPES:
@@ -182,7 +186,7 @@ class LLMEngine:
         self.model_cfg.max_position = max(self.model_cfg.max_position, cfg.max_model_len)
         if cfg.weight_quant and self.model_cfg.is_moe:
             raise ValueError(f"EngineConfig.weight_quant={cfg.weight_quant!r}: {self.model_cfg.name} is a MoE model; "
-                             f"its projections stay bf16 (expert_quant='fp8' quantises its experts)")
+                             f"its projections stay bf16 (expert_quant='fp8' or 'awq' quantises its experts)")
         if cfg.expert_quant and not self.model_cfg.is_moe:
             raise ValueError(f"EngineConfig.expert_quant={cfg.expert_quant!r}: {self.model_cfg.name} is a dense model "
                              f"(weight_quant quantises its projections)")
@@ -193,7 +197,7 @@ class LLMEngine:
                                  or getattr(self.model, "act_quant", None) != cfg.act_quant):
             # before the KV budget: the pool gets the HBM the bf16 projections give back
             self.model.quantize_weights(cfg.weight_quant, act_quant=cfg.act_quant)
-        if cfg.expert_quant and getattr(self.model, "expert_quant", None) != cfg.expert_quant:
+        if cfg.expert_quant and getattr(self.model, "expert_quant", None) != EXPERT_QUANT_KINDS[cfg.expert_quant][0]:
             # before the KV budget: the pool gets the HBM the bf16 experts give back
             self.model.quantize_experts(cfg.expert_quant)
         if self.device.type == "cuda":

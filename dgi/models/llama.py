@@ -104,6 +104,9 @@ QUANT_SLOTS = ("qkv", "o", "gate_up", "down")    # the projections quantize_weig
 QUANT_KINDS = {"fp8": (ops.Fp8Weight, ops.quantize_fp8), "mxfp4": (ops.Mxfp4Weight, ops.quantize_mxfp4),
                "int4": (ops.Int4Weight, ops.quantize_int4)}
 EXPERT_SLOTS = ("experts_gate_up", "experts_down")    # the tensors quantize_experts replaces
+# quantize_experts' modes: what LlamaModel.expert_quant then reads, the container and its quantiser
+EXPERT_QUANT_KINDS = {"fp8": ("fp8", ops.Fp8ExpertWeight, ops.quantize_fp8_experts),
+                      "awq": ("int4", ops.Int4ExpertWeight, ops.quantize_int4_experts)}
 
 
 def _rand(shape, gen, device, dtype, std):
@@ -160,7 +163,8 @@ class LlamaModel:
         self.weight_quant: Optional[str] = None
         self.act_quant: Optional[str] = None        # "fp8": W8A8 above ops.W8A8_MIN_M rows (quantize_weights)
         self._quant_scratch: Optional[torch.Tensor] = None
-        # "fp8": a MoE model's experts_gate_up / experts_down are ops.Fp8ExpertWeight (quantize_experts)
+        # "fp8" / "int4": a MoE model's experts_gate_up / experts_down are ops.Fp8ExpertWeight /
+        # ops.Int4ExpertWeight (quantize_experts; "int4" is what the public "awq" fills)
         self.expert_quant: Optional[str] = None
         # MoE models (tests): hook(global layer, positions, ids [T, k], weights [T, k]) -> ids to
         # force, or None to keep the router's choice.  Eager steps only: it reads the routing
@@ -353,21 +357,30 @@ class LlamaModel:
         becomes an ``ops.Fp8ExpertWeight`` (``ops.quantize_fp8_experts``: e4m3 codes, one fp32 scale
         per expert and output channel), layer by layer, dropping the bf16 tensors as it goes.  The
         attention projections, the router, the norms and the embeddings keep their dtype; steps run
-        the same ``ops.moe_mlp``, whose two GEMMs become ``moe_gemm_w8``.  Idempotent."""
+        the same ``ops.moe_mlp``, whose two GEMMs become ``moe_gemm_w8``.  Idempotent.
+
+        ``"awq"``, the public switches' name as for ``weight_quant``: INT4 weight-only experts,
+        ``ops.Int4ExpertWeight`` (``ops.quantize_int4_experts``: 4-bit codes, one fp16 scale and one zero
+        point per 128 elements, rounded to nearest from the bf16 weights); the two GEMMs become
+        ``moe_gemm_w4`` and ``expert_quant`` reads ``"int4"``."""
         if mode == "mxfp4":
-            raise ValueError("quantize_experts: 'mxfp4' is not supported for experts yet (supported: 'fp8')")
-        if mode != "fp8":
-            raise ValueError(f"quantize_experts: unsupported mode {mode!r} (supported: 'fp8')")
+            raise ValueError("quantize_experts: 'mxfp4' is not supported for experts yet (supported: 'fp8', 'awq')")
+        if mode not in EXPERT_QUANT_KINDS:
+            raise ValueError(f"quantize_experts: unsupported mode {mode!r} (supported: 'fp8', 'awq')")
+        mode, kind, quantise = EXPERT_QUANT_KINDS[mode]
         if not self.cfg.is_moe:
             raise ValueError(f"quantize_experts: {self.cfg.name} is a dense model; quantise its projections with "
                              "quantize_weights (EngineConfig.weight_quant)")
         if self.expert_quant == mode:
             return self
+        if self.expert_quant:
+            raise RuntimeError(f"quantize_experts: the model's experts are {self.expert_quant}-quantised already; "
+                               f"quantise a model holding the bf16 experts to {mode!r}")
         for L in self.layers:
             for k in EXPERT_SLOTS:
                 w = getattr(L, k)
-                if not isinstance(w, ops.Fp8ExpertWeight):
-                    setattr(L, k, ops.quantize_fp8_experts(w))
+                if not isinstance(w, kind):
+                    setattr(L, k, quantise(w))
                     del w
         self.expert_quant = mode
         if self.device.type == "cuda":
@@ -447,7 +460,7 @@ class LlamaModel:
         for i, L in enumerate(self.layers):
             for k in LlamaLayerWeights.__slots__:
                 t = getattr(L, k)
-                if isinstance(t, ops.Int4Weight):
+                if isinstance(t, (ops.Int4Weight, ops.Int4ExpertWeight)):
                     yield f"layers.{self.layer_start + i}.{k}.q", t.q
                     yield f"layers.{self.layer_start + i}.{k}.sz", t.sz
                 elif isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
@@ -486,7 +499,8 @@ class LlamaModel:
         for L in self.layers:
             for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias, L.q_norm, L.k_norm,
                       L.router, L.experts_gate_up, L.experts_down):
-                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Int4Weight, ops.Fp8ExpertWeight)):
+                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Int4Weight, ops.Fp8ExpertWeight,
+                                  ops.Int4ExpertWeight)):
                     # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements; int4: 4 bytes per 128)
                     n += t.nbytes()
                 elif t is not None:

@@ -22,7 +22,8 @@ import torch
 from dgi.ops.fp8 import E4M3_MAX, Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
 from dgi.ops.fp8 import Fp8ExpertWeight, quantize_fp8_experts  # noqa: F401  (public: the MoE experts' container)
 from dgi.ops.mxfp4 import Mxfp4Weight, quantize_mxfp4  # noqa: F401  (public: ops.Mxfp4Weight, ops.quantize_mxfp4)
-from dgi.ops.int4 import Int4Weight, int4_cat, int4_from_awq, quantize_int4  # noqa: F401  (public)
+from dgi.ops.int4 import (Int4ExpertWeight, Int4Weight, int4_cat, int4_from_awq, quantize_int4,  # noqa: F401  (public)
+                          quantize_int4_experts)
 
 _LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_C.so")
 _loaded = False
@@ -1459,26 +1460,36 @@ def _silu_mul_f32(gu: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.silu(gu[..., :I]) * gu[..., I:]
 
 
+_EXPERT_CONTAINERS = (Fp8ExpertWeight, Int4ExpertWeight)
+
+
 def _expert_f32(w, e: int) -> torch.Tensor:
-    """Expert ``e`` of ``w`` ([E, N, K] tensor or ``Fp8ExpertWeight``) in fp32; the container is
-    dequantised as ``linear_fp8_ref`` does (``q.float() * scale[:, None]``)."""
-    return w[e].dequant(torch.float32) if isinstance(w, Fp8ExpertWeight) else w[e].float()
+    """Expert ``e`` of ``w`` ([E, N, K] tensor, ``Fp8ExpertWeight`` or ``Int4ExpertWeight``) in fp32; a
+    container is dequantised as the dense reference of its format does (``q.float() * scale[:, None]``;
+    ``(code - zero) * scale``)."""
+    return w[e].dequant(torch.float32) if isinstance(w, _EXPERT_CONTAINERS) else w[e].float()
+
+
+def _expert_words(w):
+    """The two tensors of an expert container: codes, and scales (fp8) or scale / zero words (int4)."""
+    return w.q, (w.sz if isinstance(w, Int4ExpertWeight) else w.scale)
 
 
 def _expert_pair_quantised(gate_up, down) -> bool:
-    """Whether the block's experts are ``Fp8ExpertWeight``: both, or neither."""
-    qg, qd = isinstance(gate_up, Fp8ExpertWeight), isinstance(down, Fp8ExpertWeight)
-    if qg != qd:
-        raise ValueError("moe_mlp: gate_up and down must both be Fp8ExpertWeight or both be tensors, got "
-                         f"{type(gate_up).__name__} and {type(down).__name__}")
-    return qg
+    """Whether the block's experts are containers: both of one kind, or neither."""
+    kg = type(gate_up) if isinstance(gate_up, _EXPERT_CONTAINERS) else None
+    kd = type(down) if isinstance(down, _EXPERT_CONTAINERS) else None
+    if kg is not kd:
+        raise ValueError("moe_mlp: gate_up and down must both be Fp8ExpertWeight, both be Int4ExpertWeight or both "
+                         f"be tensors, got {type(gate_up).__name__} and {type(down).__name__}")
+    return kg is not None
 
 
 def moe_gemm_ref(x: torch.Tensor, w, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
                  epi: int, BM: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The definition of ``moe_gemm``: row p of row block b is ``A[p] · w[block_expert[b]]^T`` with
-    fp32 accumulation, rounded once to ``x.dtype``; an ``Fp8ExpertWeight`` is dequantised per expert
-    (``q.float() * scale[:, None]``).  SwiGLU (``epi`` 1, ``w = [gate; up]``): A[p] is
+    fp32 accumulation, rounded once to ``x.dtype``; an ``Fp8ExpertWeight`` or ``Int4ExpertWeight`` is
+    dequantised per expert in fp32.  SwiGLU (``epi`` 1, ``w = [gate; up]``): A[p] is
     token ``sorted_slot[p] // k`` of ``x`` and the fp32 ``silu(gate) * up`` is what is rounded; plain:
     A[p] is row p of ``x``.  Padding rows (slot -1) are left as ``out`` had them (zeros without ``out``)."""
     P = sorted_slot.numel()
@@ -1502,12 +1513,14 @@ def _moe_gemm_native(x: torch.Tensor, w: torch.Tensor, epi: int) -> bool:
             and N % 16 == 0 and w.shape[0] <= MOE_MAX_EXPERTS and x.data_ptr() % 16 == 0)
 
 
-def _moe_gemm_w8_native(x: torch.Tensor, w: Fp8ExpertWeight, epi: int) -> bool:
+def _moe_gemm_wq_native(x: torch.Tensor, w, epi: int) -> bool:
+    """Whether ``moe_gemm_w8`` / ``moe_gemm_w4`` take ``x`` and the container ``w``."""
     N = w.shape[1] // 2 if epi else w.shape[1]
-    return (x.is_cuda and w.q.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1
+    q, s = _expert_words(w)
+    return (x.is_cuda and q.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1
             and x.stride(0) % 8 == 0 and x.shape[1] % 256 == 0 and x.shape[1] == w.shape[2] and N % 16 == 0
-            and w.shape[0] <= MOE_MAX_EXPERTS and x.data_ptr() % 16 == 0 and w.q.data_ptr() % 16 == 0
-            and w.scale.data_ptr() % 16 == 0)
+            and w.shape[0] <= MOE_MAX_EXPERTS and x.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0
+            and s.data_ptr() % 16 == 0)
 
 
 def moe_gemm(x: torch.Tensor, w, sorted_slot: torch.Tensor, block_expert: torch.Tensor, k: int,
@@ -1516,9 +1529,10 @@ def moe_gemm(x: torch.Tensor, w, sorted_slot: torch.Tensor, block_expert: torch.
     ``MOE_EPI_SWIGLU`` gathers token rows of ``x [T, K]`` and applies SwiGLU over ``w [E, 2N, K]``;
     ``MOE_EPI_PLAIN`` reads ``x [P, K]`` in sorted order against ``w [E, N, K]``.  ``k`` is the experts
     per token (the slot -> token divisor).  The HIP kernel takes bf16, K % 256 == 0, N % 16 == 0.
-    ``w`` may be an ``Fp8ExpertWeight`` (``moe_gemm_w8``: e4m3 codes, per-expert per-channel scales)."""
-    if isinstance(w, Fp8ExpertWeight):
-        if not _moe_gemm_w8_native(x, w, epi):
+    ``w`` may be an ``Fp8ExpertWeight`` (``moe_gemm_w8``: e4m3 codes, per-expert per-channel scales) or an
+    ``Int4ExpertWeight`` (``moe_gemm_w4``: 4-bit codes, an fp16 scale and a zero point per 128 elements)."""
+    if isinstance(w, _EXPERT_CONTAINERS):
+        if not _moe_gemm_wq_native(x, w, epi):
             return moe_gemm_ref(x, w, sorted_slot, block_expert, k, epi, BM, out)
         load_native(required=True)
         P = sorted_slot.numel()
@@ -1526,7 +1540,8 @@ def moe_gemm(x: torch.Tensor, w, sorted_slot: torch.Tensor, block_expert: torch.
         if out is None:
             out = torch.empty(P, N, dtype=x.dtype, device=x.device)
         nslots = x.shape[0] * k if epi else P
-        _call("moe_gemm_w8", out, x, w.q, w.scale, sorted_slot, block_expert, k, nslots, epi, BM)
+        _call("moe_gemm_w4" if isinstance(w, Int4ExpertWeight) else "moe_gemm_w8", out, x, *_expert_words(w),
+              sorted_slot, block_expert, k, nslots, epi, BM)
         return out
     if _moe_gemm_native(x, w, epi):
         load_native(required=True)
@@ -1571,7 +1586,8 @@ def moe_mlp_ref(x: torch.Tensor, router_w: torch.Tensor, gate_up, down, k: int, 
     ``x.dtype``, ``moe_route_ref`` (or the forced ``ids`` with the model's own probabilities at them),
     then for every expert its tokens through ``silu(gate) * up`` (fp32, rounded to ``x.dtype``) and
     ``down`` (fp32 accumulate, rounded), combined by ``moe_combine_ref``.  ``gate_up`` and ``down``
-    may both be ``Fp8ExpertWeight``: each expert is then dequantised to fp32 first."""
+    may both be ``Fp8ExpertWeight`` or both ``Int4ExpertWeight``: each expert is then dequantised to fp32
+    first."""
     _expert_pair_quantised(gate_up, down)
     T, H = x.shape
     logits = torch.nn.functional.linear(x, router_w)
@@ -1597,8 +1613,7 @@ def moe_mlp_ok(x: torch.Tensor, router_w: torch.Tensor, gate_up, down, k: int) -
     if _expert_pair_quantised(gate_up, down):
         return (x.is_cuda and x.dim() == 2 and x.shape[0] > 0 and x.dtype == torch.bfloat16
                 and gate_up.q.is_cuda and down.q.is_cuda and H % 256 == 0 and (I2 // 2) % 256 == 0
-                and gate_up.q.data_ptr() % 16 == 0 and gate_up.scale.data_ptr() % 16 == 0
-                and down.q.data_ptr() % 16 == 0 and down.scale.data_ptr() % 16 == 0
+                and all(t.data_ptr() % 16 == 0 for t in _expert_words(gate_up) + _expert_words(down))
                 and E <= MOE_MAX_EXPERTS and 1 <= k <= min(E, MOE_MAX_TOPK) and x.shape[0] * k < (1 << 30))
     return (x.is_cuda and x.dim() == 2 and x.shape[0] > 0 and x.dtype == torch.bfloat16
             and gate_up.dtype == torch.bfloat16 and down.dtype == torch.bfloat16
@@ -1614,7 +1629,8 @@ def moe_mlp(x: torch.Tensor, router_w: torch.Tensor, gate_up, down, k: int, norm
     -> ``moe_gemm`` (plain) -> ``moe_combine``; nothing is read back, so the block captures into a
     graph.  ``ids`` forces the routing (tests): the weights are then the model's own softmax
     probabilities at those ids.  FP8 weight-only experts: ``gate_up`` and ``down`` both as
-    ``Fp8ExpertWeight`` (a mix raises); the two GEMMs are then ``moe_gemm_w8``, nothing else changes."""
+    ``Fp8ExpertWeight`` (a mix raises); the two GEMMs are then ``moe_gemm_w8``, nothing else changes.
+    INT4 weight-only experts: both as ``Int4ExpertWeight``; the two GEMMs are then ``moe_gemm_w4``."""
     if not moe_mlp_ok(x, router_w, gate_up, down, k):
         return moe_mlp_ref(x, router_w, gate_up, down, k, norm_topk, ids)
     T = x.shape[0]

@@ -6,6 +6,9 @@ the weight container, a round-to-nearest quantiser and the repacker of AWQ check
 ``code`` and ``zero`` are integers in 0..15, ``scale`` is a finite fp16, the group is 128 elements
 of a row.  Activations, accumulation and outputs stay as they are.  ``dgi.ops.linear`` takes an
 ``Int4Weight`` wherever it takes a weight tensor.
+
+The experts of a MoE layer are held the same way, stacked: ``Int4ExpertWeight``, which
+``dgi.ops.moe_gemm`` / ``moe_mlp`` take wherever they take an ``[E, N, K]`` tensor.
 """
 from __future__ import annotations
 
@@ -150,6 +153,67 @@ def quantize_int4(w: torch.Tensor) -> Int4Weight:
             zero[r0:r0 + step] = z.to(torch.uint8)
             scale[r0:r0 + step] = s16
     return Int4Weight.pack(code, zero, scale)
+
+
+class Int4ExpertWeight:
+    """The experts of a MoE layer, INT4 weight-only: ``Int4Weight``'s row layout stacked over experts,
+    ``q`` [E, N, K/8] int32 and ``sz`` [E, N, K/128] int32 (rows are independent, so ``[gate; up]`` and
+    the expert index are row offsets).  ``dgi.ops.moe_gemm`` / ``moe_mlp`` take it wherever they take
+    an ``[E, N, K]`` tensor."""
+    __slots__ = ("q", "sz")
+
+    def __init__(self, q: torch.Tensor, sz: torch.Tensor):
+        if q.dtype != torch.int32 or q.dim() != 3 or not q.is_contiguous() or (8 * q.shape[2]) % INT4_GROUP:
+            raise ValueError("Int4ExpertWeight: q must be a contiguous [E, N, K/8] int32 tensor with K % 128 == 0")
+        if (sz.dtype != torch.int32 or sz.shape != (q.shape[0], q.shape[1], 8 * q.shape[2] // INT4_GROUP)
+                or not sz.is_contiguous()):
+            raise ValueError("Int4ExpertWeight: sz must be a contiguous [E, N, K/128] int32 tensor")
+        if sz.device != q.device:
+            raise ValueError("Int4ExpertWeight: q and sz must be on one device")
+        self.q = q
+        self.sz = sz
+
+    @property
+    def shape(self) -> torch.Size:
+        return torch.Size((self.q.shape[0], self.q.shape[1], 8 * self.q.shape[2]))
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    def nbytes(self) -> int:
+        return 4 * (self.q.numel() + self.sz.numel())
+
+    def __getitem__(self, e: int) -> Int4Weight:
+        """Expert ``e`` as a dense ``Int4Weight`` (views of the codes and scale words, nothing copied)."""
+        return Int4Weight(self.q[e], self.sz[e])
+
+    def dequant(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """``(code - zero) * scale`` in fp32, rounded once to ``dtype``: ``[E, N, K]``, one expert at a time."""
+        out = torch.empty(tuple(self.shape), dtype=dtype, device=self.q.device)
+        for e in range(self.q.shape[0]):
+            out[e] = self[e].dequant(dtype)
+        return out
+
+    def __repr__(self) -> str:
+        return f"Int4ExpertWeight(shape={tuple(self.shape)}, device={self.q.device})"
+
+
+def quantize_int4_experts(w: torch.Tensor) -> Int4ExpertWeight:
+    """``quantize_int4`` of every expert of ``w [E, N, K]``, written into one ``Int4ExpertWeight``:
+    bit-identical words to ``quantize_int4(w[e])``, one expert at a time (the temporaries are those of
+    one expert's quantiser)."""
+    if w.dim() != 3 or w.shape[2] % INT4_GROUP:
+        raise ValueError("quantize_int4_experts: an [E, N, K] weight with K % 128 == 0")
+    E, N, K = w.shape
+    q = torch.empty(E, N, K // 8, dtype=torch.int32, device=w.device)
+    sz = torch.empty(E, N, K // INT4_GROUP, dtype=torch.int32, device=w.device)
+    for e in range(E):
+        one = quantize_int4(w[e])
+        q[e].copy_(one.q)
+        sz[e].copy_(one.sz)
+        del one
+    return Int4ExpertWeight(q, sz)
 
 
 def _awq_unpack(packed: torch.Tensor) -> torch.Tensor:

@@ -412,9 +412,11 @@ def main(argv=None) -> int:
     ap.add_argument("--kv-dtype", default=None, choices=["fp8"],
                     help="KV cache pages as e4m3 codes with per-head scales (default: bf16 pages); "
                          "single-GPU engines only")
-    ap.add_argument("--expert-quant", default=None, choices=["fp8"],
-                    help="MoE models: FP8 weight-only experts (e4m3 codes, per-expert per-channel scales); the "
-                         "attention projections stay bf16 (default: bf16 experts); single-GPU engine only")
+    ap.add_argument("--expert-quant", default=None, choices=["fp8", "awq"],
+                    help="MoE models: weight-only experts, fp8 (e4m3 codes, per-expert per-channel scales) or awq "
+                         "(int4: 4-bit codes, an fp16 scale and a zero point per 128 elements, rounded to nearest "
+                         "from bf16); the attention projections stay bf16 (default: bf16 experts); single-GPU "
+                         "engine only")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.expert_quant and world > 1:

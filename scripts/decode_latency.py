@@ -31,7 +31,8 @@ def main():
     ap.add_argument("--prefill-tokens", type=int, default=0,
                     help="also time one prefill step of this many tokens (one prompt, after the decode batches)")
     ap.add_argument("--kv-dtype", default=None, choices=["fp8"], help="fp8 (e4m3) KV cache pages")
-    ap.add_argument("--expert-quant", default=None, choices=["fp8"], help="MoE models: FP8 weight-only experts")
+    ap.add_argument("--expert-quant", default=None, choices=["fp8", "awq"],
+                    help="MoE models: weight-only experts, fp8 (e4m3) or awq (int4, group scales and zero points)")
     ap.add_argument("--num-blocks", type=int, default=None, help="KV pages (default: from free memory)")
     a = ap.parse_args()
     cfg = EngineConfig(model=a.model, device="cuda", max_num_seqs=max(a.batch), max_num_batched_tokens=8192,

@@ -19,7 +19,8 @@ Config keys accepted (SURVEY Appendix C mapping): ``model_id``, ``device``,
 weight-only 4-bit projections with group scales and zero points, read from an AWQ checkpoint or rounded from bf16;
 anything else is served unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
 ``DGI_W8A8_MIN_M`` rows, default 2048; ``quantization: "fp8"`` alone stays W8A16), ``expert_quant`` (``"fp8"``:
-weight-only e4m3 experts of a MoE model; anything else, or a dense model, is served with bf16 experts); nested ``sglang``/``vllm``/
+weight-only e4m3 experts of a MoE model, ``"awq"``: weight-only 4-bit experts with group scales and zero points,
+rounded from bf16; anything else, or a dense model, is served with bf16 experts); nested ``sglang``/``vllm``/
 ``native`` dicts are merged in.
 
 Sliding-window attention needs no key: a Mistral config (``sliding_window`` on every layer) or a Qwen2
@@ -130,13 +131,13 @@ class NativeLLMEngine(LLMBaseEngine):
             logger.warning("act_quant=%r is not supported by the native engine (supported: 'fp8', together with "
                            "quantization 'fp8'); serving %s with bf16 activations", actq, model_id)
             actq = None
-        # FP8 weight-only experts are opt-in, and a MoE model's knob only
+        # weight-only experts (fp8, or awq: int4) are opt-in, and a MoE model's knob only
         expq = c.get("expert_quant")
         if expq is not None and str(expq).lower() in ("", "none"):
             expq = None
-        if expq is not None and (str(expq).lower() != "fp8" or not mc.is_moe):
-            logger.warning("expert_quant=%r is not supported by the native engine (supported: 'fp8', for a MoE "
-                           "model); serving %s with bf16 experts", expq, model_id)
+        if expq is not None and (str(expq).lower() not in ("fp8", "awq") or not mc.is_moe):
+            logger.warning("expert_quant=%r is not supported by the native engine (supported: 'fp8' and 'awq', for "
+                           "a MoE model); serving %s with bf16 experts", expq, model_id)
             expq = None
         # vLLM / SGLang name it kv_cache_dtype; "auto" and the activation dtypes mean no KV quantisation
         kvd = c.get("kv_cache_dtype", c.get("kv_dtype"))
@@ -159,7 +160,7 @@ class NativeLLMEngine(LLMBaseEngine):
             host_kv_gb=float(c.get("host_kv_gb", 0.0)), weight_quant=quant,
             act_quant="fp8" if actq is not None else None,
             kv_dtype="fp8" if kvd is not None else None,
-            expert_quant="fp8" if expq is not None else None,
+            expert_quant=str(expq).lower() if expq is not None else None,
             graph_buckets=tuple(c["graph_batch_buckets"]) if c.get("graph_batch_buckets") else None)
         spec = c.get("speculative")
         if spec:

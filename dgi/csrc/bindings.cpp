@@ -39,6 +39,9 @@ int dgi_skinny_gemm(const void* x, int ldx, const void* w, const void* bias, voi
 int dgi_skinny_gemm_w8(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
                        int ldy, int M, int N, int K, int cfg, hipStream_t s);
 int dgi_dequant_fp8(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
+int dgi_skinny_gemm_w8b(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
+                        int ldy, int M, int N, int K, int cfg, hipStream_t s);
+int dgi_dequant_fp8_block(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
 int dgi_skinny_gemm_w4(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y,
                        int ldy, int M, int N, int K, int cfg, hipStream_t s);
 int dgi_dequant_mxfp4(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s);
@@ -529,6 +532,47 @@ void dequant_fp8(at::Tensor out, const at::Tensor& wq, const at::Tensor& scale) 
   check_rc(dgi_dequant_fp8(wq.data_ptr(), scale.data_ptr(), out.data_ptr(), (int)wq.size(0), (int)wq.size(1),
                            cur_stream()),
            "dequant_fp8");
+}
+
+// wq [N, K] e4m3 and scale [N/16, K/128] fp32 of a block-scaled FP8 weight: N % 16 == 0, K % 128 == 0
+static void check_fp8_block(const char* name, const at::Tensor& wq, const at::Tensor& scale) {
+  check_dev(wq, "wq"); check_dev(scale, "scale");
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn, name, ": wq must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, name, ": scale must be float32");
+  TORCH_CHECK(wq.dim() == 2 && scale.dim() == 2 && wq.is_contiguous() && scale.is_contiguous(), name,
+              ": wq and scale row-major 2-D");
+  const int64_t N = wq.size(0), K = wq.size(1);
+  TORCH_CHECK(N % 16 == 0 && K % 128 == 0 && scale.size(0) * 16 == N && scale.size(1) * 128 == K &&
+                  N < (1LL << 31) && K < (1LL << 31),
+              name, ": wq [N, K] with N%16 and K%128, scale [N/16, K/128]");
+  TORCH_CHECK(wq.device() == scale.device(), name, ": operands on one device");
+  TORCH_CHECK((uintptr_t)wq.data_ptr() % 16 == 0 && (uintptr_t)scale.data_ptr() % 4 == 0, name,
+              ": wq 16-byte aligned, scale 4-byte aligned");
+}
+
+// W8A16 decode GEMM over block-scaled weights: out = x (wq * scale[n / 16, k / 128])^T (+ bias)
+void skinny_gemm_w8b(at::Tensor out, const at::Tensor& x, const at::Tensor& wq, const at::Tensor& scale,
+                     const c10::optional<at::Tensor>& bias, int64_t cfg) {
+  check_fp8_block("skinny_gemm_w8b", wq, scale);
+  TORCH_CHECK(wq.device() == x.device(), "skinny_gemm_w8b: operands on one device");
+  const int64_t N = wq.size(0), K = wq.size(1);
+  const void* b = check_skinny_operands("skinny_gemm_w8b", out, x, N, K, bias);
+  check_rc(dgi_skinny_gemm_w8b(x.data_ptr(), (int)x.stride(0), wq.data_ptr(), scale.data_ptr(), b, out.data_ptr(),
+                               (int)out.stride(0), (int)x.size(0), (int)N, (int)K, (int)cfg, cur_stream()),
+           "skinny_gemm_w8b");
+}
+
+// out [N, K] bf16 = bf16(float(wq) * scale[n / 16, k / 128]) (the route of every shape skinny_gemm_w8b does not take)
+void dequant_fp8_block(at::Tensor out, const at::Tensor& wq, const at::Tensor& scale) {
+  check_bf16(out, "out");
+  check_fp8_block("dequant_fp8_block", wq, scale);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == wq.size(0) && out.size(1) == wq.size(1) && out.is_contiguous(),
+              "dequant_fp8_block: out is a contiguous [N, K]");
+  TORCH_CHECK(out.device() == wq.device() && (uintptr_t)out.data_ptr() % 16 == 0,
+              "dequant_fp8_block: out on wq's device, 16-byte aligned");
+  check_rc(dgi_dequant_fp8_block(wq.data_ptr(), scale.data_ptr(), out.data_ptr(), (int)wq.size(0), (int)wq.size(1),
+                                 cur_stream()),
+           "dequant_fp8_block");
 }
 
 // W4A16 decode GEMM over MXFP4 weights: out = x w^T (+ bias); q [N, K/2] bytes of two e2m1 codes (low nibble
@@ -1061,6 +1105,8 @@ TORCH_LIBRARY(dgi, m) {
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int cfg=0) -> ()");
   m.def("skinny_gemm_w8(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");
   m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
+  m.def("skinny_gemm_w8b(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale, Tensor? bias, int cfg=0) -> ()");
+  m.def("dequant_fp8_block(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
   m.def("skinny_gemm_w4(Tensor(a!) out, Tensor x, Tensor q, Tensor scale, Tensor? bias, int cfg=0) -> ()");
   m.def("dequant_mxfp4(Tensor(a!) out, Tensor q, Tensor scale) -> ()");
   m.def("skinny_gemm_i4(Tensor(a!) out, Tensor x, Tensor q, Tensor sz, Tensor? bias, int cfg=0) -> ()");
@@ -1110,6 +1156,8 @@ TORCH_LIBRARY_IMPL(dgi, CUDA, m) {
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("skinny_gemm_w8", &skinny_gemm_w8);
   m.impl("dequant_fp8", &dequant_fp8);
+  m.impl("skinny_gemm_w8b", &skinny_gemm_w8b);
+  m.impl("dequant_fp8_block", &dequant_fp8_block);
   m.impl("skinny_gemm_w4", &skinny_gemm_w4);
   m.impl("dequant_mxfp4", &dequant_mxfp4);
   m.impl("skinny_gemm_i4", &skinny_gemm_i4);

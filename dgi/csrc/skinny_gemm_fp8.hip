@@ -8,6 +8,13 @@
 // The design is stream_gemm.h's, with half the weight bytes of bf16: a K step is 128 deep and
 // the lane's 32 e4m3 values are widened in registers to four B fragments (E4m3W).  The epilogue
 // multiplies the fp32 sum by scale[col], adds the bias and rounds once.
+//
+// skinny_gemm_w8b is the same stream over block-scaled weights (E4m3BlockW): one fp32 scale per
+// 16-row tile and 128-deep K step, scale [N/16, K/128] — what the 128 x 128 blocks of the
+// published FP8 checkpoints become at load.  The scale varies along K, so it cannot wait for the
+// epilogue: each step's four MFMAs run into a group accumulator that is folded into the tile's
+// accumulator with one fp32 fma per register, scale * group + acc.  The codes are never scaled,
+// the bytes per step and hence the launch geometries are skinny_gemm_w8's.
 #include "stream_gemm.h"
 
 using namespace dgi;
@@ -36,6 +43,27 @@ int launch(const void* x, int ldx, const void* w, const void* scale, const void*
                                                           scale, bias, y, ldy, M, K);
 }
 
+template <int NW, int MT, int NT, int U, int D>
+__global__ __launch_bounds__(NW * 64) void skinny_gemm_w8b_kernel(
+    const uint16_t* __restrict__ X, int ldx, const uint8_t* __restrict__ W, const float* __restrict__ scale,
+    const uint16_t* __restrict__ bias, uint16_t* __restrict__ Y, int ldy, int M, int K) {
+  stream_gemm_dense<E4m3BlockW, NW, MT, NT, U, D>(X, ldx, E4m3BlockW::Mat{W, scale}, Y, ldy, M, K,
+                                                  [&](f32x4 v, int col) {
+    const float b = bias ? bf16_to_f32(bias[col]) : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = v[i] + b;
+    return v;
+  });
+}
+
+template <int NW, int NT, int U, int D>
+int launch_block(const void* x, int ldx, const void* w, const void* scale, const void* bias, void* y, int ldy, int M,
+                 int N, int K, hipStream_t s) {
+  return launch_stream_dense<E4m3BlockW::kStep, NW, U, NT, NT>(skinny_gemm_w8b_kernel<NW, 1, NT, U, D>,
+                                                               skinny_gemm_w8b_kernel<NW, 2, NT, U, D>, M, N, K, s, x,
+                                                               ldx, w, scale, bias, y, ldy, M, K);
+}
+
 // 16 e4m3 in, 16 bf16 out per thread; K % 16 == 0 keeps a chunk inside one row (one scale)
 __global__ __launch_bounds__(256) void dequant_fp8_kernel(const u32x4* __restrict__ Wq,
                                                           const float* __restrict__ scale,
@@ -43,6 +71,28 @@ __global__ __launch_bounds__(256) void dequant_fp8_kernel(const u32x4* __restric
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= chunks) return;
   const float sc = scale[i / K16];
+  const u32x4 v = __builtin_nontemporal_load(Wq + i);
+  u32x4 o[2];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x2v lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[q], false);
+    const f32x2v hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[q], true);
+    o[q >> 1][2 * (q & 1)] = pack_bf16x2(lo[0] * sc, lo[1] * sc);
+    o[q >> 1][2 * (q & 1) + 1] = pack_bf16x2(hi[0] * sc, hi[1] * sc);
+  }
+  out[2 * i] = o[0];
+  out[2 * i + 1] = o[1];
+}
+
+// the same over block scales: chunk c of row n lies in tile n / 16 and K step c / 8
+__global__ __launch_bounds__(256) void dequant_fp8_block_kernel(const u32x4* __restrict__ Wq,
+                                                                const float* __restrict__ scale,
+                                                                u32x4* __restrict__ out, long long chunks, int K16) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= chunks) return;
+  const long long row = i / K16;
+  const int c = (int)(i - row * K16);
+  const float sc = scale[(row >> 4) * (K16 >> 3) + (c >> 3)];
   const u32x4 v = __builtin_nontemporal_load(Wq + i);
   u32x4 o[2];
 #pragma unroll
@@ -91,6 +141,40 @@ extern "C" int dgi_dequant_fp8(const void* wq, const void* scale, void* out, int
   if (blocks > 0x7fffffffLL) return -2;
   dequant_fp8_kernel<<<dim3((unsigned)blocks), 256, 0, s>>>((const u32x4*)wq, (const float*)scale, (u32x4*)out,
                                                             chunks, K / 16);
+  DGI_CHECK_LAUNCH();
+  return 0;
+}
+
+// skinny_gemm_w8 over block scales: scale [N/16, K/128] fp32, one per 16-row tile and 128-deep step.
+// The configs, their requirements and the return codes are dgi_skinny_gemm_w8's.
+extern "C" int dgi_skinny_gemm_w8b(const void* x, int ldx, const void* w, const void* scale, const void* bias,
+                                   void* y, int ldy, int M, int N, int K, int cfg, hipStream_t s) {
+  if (M <= 0 || N <= 0) return 0;
+  if (M > 32) return -2;
+  if (K % 1024 || N % 16 || ldx % 8) return -3;
+  if (cfg == 0) cfg = 2;
+  switch (cfg) {
+    case 1: return launch_block<8, 1, 1, 4>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);
+    case 2: return launch_block<8, 1, 1, 2>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);
+    case 3: return launch_block<4, 1, 2, 2>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);
+    case 4: return launch_block<4, 1, 2, 4>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);
+    case 5: return launch_block<8, 2, 1, 2>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);   // N % 32
+    case 6: return launch_block<4, 1, 1, 8>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);
+    case 7: return launch_block<16, 1, 1, 2>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);  // K % 2048
+    case 8: return launch_block<8, 4, 1, 2>(x, ldx, w, scale, bias, y, ldy, M, N, K, s);   // N % 64
+    default: return -4;
+  }
+}
+
+// out[N, K] (bf16) = round(float(Wq[N, K]) * scale[n / 16, k / 128]); N % 16 == 0, K % 128 == 0.
+extern "C" int dgi_dequant_fp8_block(const void* wq, const void* scale, void* out, int N, int K, hipStream_t s) {
+  if (N <= 0 || K <= 0) return 0;
+  if (K % 128 || N % 16) return -3;
+  const long long chunks = (long long)N * (K / 16);
+  const long long blocks = (chunks + 255) / 256;
+  if (blocks > 0x7fffffffLL) return -2;
+  dequant_fp8_block_kernel<<<dim3((unsigned)blocks), 256, 0, s>>>((const u32x4*)wq, (const float*)scale,
+                                                                  (u32x4*)out, chunks, K / 16);
   DGI_CHECK_LAUNCH();
   return 0;
 }

@@ -35,7 +35,10 @@
 // so an MFMA never mixes two groups), each run of kGroupFrags fragments is multiplied into a
 // group accumulator of its own, next to the group's row sums of X (the same fragments against a
 // B operand of ones, once for all weight tiles), and Format::fold adds the group to the tile's
-// accumulator in fp32.  kGroupFrags = 0 is the plain path, unchanged.
+// accumulator in fp32.  kGroupFrags = 0 is the plain path, unchanged.  Two compile-time flags of a
+// grouped format: kNaturalK (false: the lane's bytes stay contiguous, as on the plain path — right
+// where a whole step is one group) and kRowSums (false: a format without a zero point issues no
+// row-sum MFMAs and folds with fold(acc, group, wfrag, h)).
 //
 // Not here: fused_decode.hip.  Its three kernels interleave the norm prologue and a persistent
 // tile cursor with the ring; sharing that is a different job.
@@ -93,6 +96,54 @@ struct E4m3W {
   static __device__ __forceinline__ bf16x8 b_operand(const WFrag& f, NoScales, int q) {
     const u32x4& v = f.v[q >> 1];
     return widen8(v[2 * (q & 1)], v[2 * (q & 1) + 1]);
+  }
+};
+
+// E4m3W's codes with one fp32 scale per 16-row weight tile and 128-deep K step (the 128 x 128 block
+// scales of the published FP8 checkpoints, expanded to 16 rows at load): w[n, k] = code[n, k] *
+// s[n / 16, k / 128], s [N/16, K/128].  A block scale is no power of two, so it stays out of the B
+// operand: a step is one group of the core's grouped path, the codes are widened exactly as
+// E4m3W's (same bytes, same K order inside the step), the step's four MFMAs run into a group
+// accumulator and fold adds scale * group in fp32.  There is no zero point, hence no row sums.
+// The scale of (tile, step) is the same for every lane of the wave: its address is made uniform
+// (readfirstlane), so it arrives through the scalar cache, and it is loaded with the step's codes
+// into the ring — the fold waits on nothing.
+struct E4m3BlockW {
+  static constexpr int kStep = 128, kXFrags = 4, kGroupFrags = 4;
+  static constexpr bool kNaturalK = false, kRowSums = false;
+  struct Mat {
+    const uint8_t* q;
+    const float* s;
+  };
+  using Ptr = Mat;
+  struct WFrag {
+    u32x4 v[2];
+    float s;
+  };
+  // rows n0 .. n0 + 15 of a tile share row >> 4; wave w starts at step w
+  static __device__ __forceinline__ Ptr ptr(Mat W, size_t row, int K, int g, int w) {
+    const int tile = __builtin_amdgcn_readfirstlane((int)(row >> 4));
+    const int w0 = __builtin_amdgcn_readfirstlane(w);
+    return Ptr{W.q + row * K + g * 32 + (size_t)w * 128, W.s + (size_t)tile * (K >> 7) + w0};
+  }
+  static __device__ __forceinline__ Ptr rows(Ptr p, size_t n, int K) {
+    return Ptr{p.q + n * K, p.s + (n >> 4) * (K >> 7)};
+  }
+  static __device__ __forceinline__ void load(WFrag& f, Ptr p, size_t step) {
+    const u32x4* q = reinterpret_cast<const u32x4*>(p.q + step * 128);
+    f.v[0] = __builtin_nontemporal_load(q);
+    f.v[1] = __builtin_nontemporal_load(q + 1);
+    f.s = p.s[step];
+  }
+  static __device__ __forceinline__ bf16x8 b_operand(const WFrag& f, NoScales, int q) {
+    const u32x4& v = f.v[q >> 1];
+    return widen8(v[2 * (q & 1)], v[2 * (q & 1) + 1]);
+  }
+  // one explicit fma per accumulator register and step: every instantiation rounds alike
+  static __device__ __forceinline__ f32x4 fold(f32x4 acc, f32x4 ag, const WFrag& f, int) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(f.s, ag[i], acc[i]);
+    return acc;
   }
 };
 
@@ -167,6 +218,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct Int4W {
   static constexpr int kStep = 256, kXFrags = 8, kGroupFrags = 4;
+  static constexpr bool kNaturalK = true, kRowSums = true;
   struct Mat {
     const uint32_t* q;
     const uint32_t* sz;
@@ -233,6 +285,13 @@ struct Int4GroupW : Int4W {
   }
 };
 
+// whether a format's fragments take the natural K order (grouped formats say; the plain path never does)
+template <class F>
+constexpr bool natural_k() {
+  if constexpr (F::kGroupFrags > 0) return F::kNaturalK;
+  else return false;
+}
+
 // Fragments of U K-steps: W for WT weight tiles, X for MT row tiles.
 template <class F, int MT, int WT, int U>
 struct StreamFrag {
@@ -257,6 +316,7 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
   const int g = lane >> 4;
   const int ngroups = (K >> __builtin_ctz(F::kStep)) / (NW * U);
   constexpr bool kGrouped = F::kGroupFrags > 0;
+  constexpr bool kNatural = natural_k<F>();
   typename F::Ptr wrow[WT];
 #pragma unroll
   for (int t = 0; t < WT; ++t) wrow[t] = wptr_of(t, r, g, w);
@@ -266,9 +326,9 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
   for (int mt = 0; mt < MT; ++mt) {
     const int row = xrow_of(mt * 16 + r);
     xval[mt] = row >= 0;
-    // lane group g: a quarter of the step (fragments 8 elements apart), or, for a grouped format,
-    // its 8 elements of every 32 (fragments 32 apart: the MFMA's own A layout)
-    xrow[mt] = X + (size_t)(xval[mt] ? row : 0) * ldx + g * (kGrouped ? 8 : F::kStep / 4) + w * F::kStep;
+    // lane group g: a quarter of the step (fragments 8 elements apart), or, for a format in the
+    // natural K order, its 8 elements of every 32 (fragments 32 apart: the MFMA's own A layout)
+    xrow[mt] = X + (size_t)(xval[mt] ? row : 0) * ldx + g * (kNatural ? 8 : F::kStep / 4) + w * F::kStep;
   }
   f32x4 acc[MT][WT];
 #pragma unroll
@@ -288,7 +348,7 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
         if (xval[mt]) {
           const u32x4* p = reinterpret_cast<const u32x4*>(xrow[mt] + step * F::kStep);
 #pragma unroll
-          for (int q = 0; q < F::kXFrags; ++q) f.x[u][mt][q] = p[kGrouped ? 4 * q : q];
+          for (int q = 0; q < F::kXFrags; ++q) f.x[u][mt][q] = p[kNatural ? 4 * q : q];
         } else {  // rows that do not exist read nothing
 #pragma unroll
           for (int q = 0; q < F::kXFrags; ++q) f.x[u][mt][q] = u32x4{0u, 0u, 0u, 0u};
@@ -306,12 +366,14 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
           // the group's row sums of X: every column of X · 1 is the sum, so the lane holds rows
           // 4g .. 4g + 3 of it next to the same rows of its accumulators
           f32x4 xs[MT];
+          if constexpr (F::kRowSums) {
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            xs[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int mt = 0; mt < MT; ++mt) {
+              xs[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int q = h * GF; q < (h + 1) * GF; ++q)
-              xs[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[u][mt][q]), F::ones(), xs[mt], 0, 0, 0);
+              for (int q = h * GF; q < (h + 1) * GF; ++q)
+                xs[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[u][mt][q]), F::ones(), xs[mt], 0, 0, 0);
+            }
           }
 #pragma unroll
           for (int t = 0; t < WT; ++t) {
@@ -326,7 +388,12 @@ __device__ __forceinline__ void stream_gemm(const uint16_t* __restrict__ X, int 
                 ag[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.x[u][mt][q]), b, ag[mt], 0, 0, 0);
             }
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt][t] = F::fold(acc[mt][t], ag[mt], xs[mt], f.w[u][t], h);
+            for (int mt = 0; mt < MT; ++mt) {
+              if constexpr (F::kRowSums)
+                acc[mt][t] = F::fold(acc[mt][t], ag[mt], xs[mt], f.w[u][t], h);
+              else
+                acc[mt][t] = F::fold(acc[mt][t], ag[mt], f.w[u][t], h);
+            }
           }
         }
     } else {

@@ -158,8 +158,8 @@ class LlamaModel:
         self.norms_folded = False    # fold_norms ran: in_norm / post_norm are ones, qkv / gate_up carry the gains
         self.fold_impl = None        # rows -> run the fused-norm layers? (dgi.runtime.gemm_pad)
         self._ss_buf: Optional[torch.Tensor] = None
-        # "fp8" / "mxfp4" / "int4": the four projections per layer are ops.Fp8Weight / ops.Mxfp4Weight /
-        # ops.Int4Weight
+        # "fp8" / "mxfp4" / "int4": the four projections per layer are ops.Fp8Weight (or, loaded from a
+        # block-FP8 checkpoint, ops.Fp8BlockWeight) / ops.Mxfp4Weight / ops.Int4Weight
         self.weight_quant: Optional[str] = None
         self.act_quant: Optional[str] = None        # "fp8": W8A8 above ops.W8A8_MIN_M rows (quantize_weights)
         self._quant_scratch: Optional[torch.Tensor] = None
@@ -326,12 +326,16 @@ class LlamaModel:
 
     def _adopt_quantised(self, mode: str, kind, quantise=None) -> None:
         """Quantise the projections that are not ``kind`` yet (a loader may have put them there),
-        share the dequantisation scratch among them and mark the model ``mode``-quantised."""
+        share the dequantisation scratch among them and mark the model ``mode``-quantised.  Without a
+        quantiser (a loaded checkpoint) a projection that is not ``kind`` is one the checkpoint keeps
+        in bf16, and stays a tensor."""
         largest = 0
         for L in self.layers:
             for k in QUANT_SLOTS:
                 w = getattr(L, k)
                 if not isinstance(w, kind):
+                    if quantise is None:
+                        continue
                     setattr(L, k, quantise(w))
                     del w
                 N, K = getattr(L, k).shape
@@ -342,14 +346,21 @@ class LlamaModel:
             self._quant_scratch = torch.empty(largest, dtype=torch.bfloat16, device=self.device)
             for L in self.layers:
                 for k in QUANT_SLOTS:
-                    getattr(L, k).scratch = self._quant_scratch
+                    if isinstance(getattr(L, k), kind):
+                        getattr(L, k).scratch = self._quant_scratch
         self.weight_quant = mode
 
     def _set_act_quant(self, act_quant: Optional[str]) -> None:
         if self.weight_quant == "fp8":      # mxfp4 and int4 weights have no activation mode (quantize_weights refuses one)
-            for L in self.layers:
-                for k in QUANT_SLOTS:
-                    getattr(L, k).act = act_quant
+            slots = [getattr(L, k) for L in self.layers for k in QUANT_SLOTS]
+            if any(isinstance(w, ops.Fp8BlockWeight) for w in slots):
+                # a block-FP8 checkpoint: W8A16 only, and nothing to mark
+                if act_quant:
+                    raise ValueError(f"quantize_weights: act_quant={act_quant!r} is not supported over block-scaled "
+                                     "fp8 weights (the e4m3 x e4m3 GEMM takes per-channel scales)")
+                slots = []
+            for w in slots:
+                w.act = act_quant
         self.act_quant = act_quant
 
     def quantize_experts(self, mode: str = "fp8") -> "LlamaModel":
@@ -463,7 +474,7 @@ class LlamaModel:
                 if isinstance(t, (ops.Int4Weight, ops.Int4ExpertWeight)):
                     yield f"layers.{self.layer_start + i}.{k}.q", t.q
                     yield f"layers.{self.layer_start + i}.{k}.sz", t.sz
-                elif isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
+                elif isinstance(t, (ops.Fp8Weight, ops.Fp8BlockWeight, ops.Mxfp4Weight, ops.Fp8ExpertWeight)):
                     yield f"layers.{self.layer_start + i}.{k}.q", t.q
                     yield f"layers.{self.layer_start + i}.{k}.scale", t.scale
                 elif t is not None:
@@ -499,9 +510,10 @@ class LlamaModel:
         for L in self.layers:
             for t in (L.in_norm, L.qkv, L.o, L.post_norm, L.gate_up, L.down, L.qkv_bias, L.q_norm, L.k_norm,
                       L.router, L.experts_gate_up, L.experts_down):
-                if isinstance(t, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Int4Weight, ops.Fp8ExpertWeight,
-                                  ops.Int4ExpertWeight)):
-                    # codes + scales (fp8: one fp32 per row; mxfp4: one byte per 32 elements; int4: 4 bytes per 128)
+                if isinstance(t, (ops.Fp8Weight, ops.Fp8BlockWeight, ops.Mxfp4Weight, ops.Int4Weight,
+                                  ops.Fp8ExpertWeight, ops.Int4ExpertWeight)):
+                    # codes + scales (fp8: one fp32 per row, or per 16 x 128 block; mxfp4: one byte per 32 elements;
+                    # int4: 4 bytes per 128)
                     n += t.nbytes()
                 elif t is not None:
                     n += t.numel() * t.element_size()

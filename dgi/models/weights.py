@@ -110,6 +110,9 @@ class CheckpointReader:
 def _put(dst: torch.Tensor, src: torch.Tensor) -> None:
     if tuple(dst.shape) != tuple(src.shape):
         raise ValueError(f"checkpoint tensor shape {tuple(src.shape)} != model slot {tuple(dst.shape)}")
+    if src.dtype == torch.float8_e4m3fn:      # codes without their scales are not the weight
+        raise ValueError(f"checkpoint tensor of shape {tuple(src.shape)} is float8_e4m3fn where a plain weight is "
+                         "expected (an FP8 LM head or embedding is not supported: list it in modules_to_not_convert)")
     dst.copy_(src.to(dst.dtype), non_blocking=False)
 
 
@@ -132,26 +135,87 @@ def load_kv_scales(rd, layer_start: int, layer_end: int, num_kv_heads: int) -> O
 
 
 AWQ_SUPPORTED = "quant_method 'awq' with bits 4, group_size 128, zero_point true and version 'gemm'"
+FP8_BLOCK_SUPPORTED = ("quant_method 'fp8' with fmt 'e4m3', weight_block_size [128, 128] and activation_scheme "
+                       "'dynamic'")
 
 
-def checkpoint_quantization(path: str) -> Optional[str]:
-    """``"int4"`` for a checkpoint whose ``config.json`` declares the one pre-quantised format that is
-    read (``AWQ_SUPPORTED``), None for one without ``quantization_config``; every other declared
-    format — other methods (all of GPTQ), bit widths, group sizes, versions — is a ValueError."""
+def _quantization_config(path: str) -> Optional[dict]:
     cfg = os.path.join(path, "config.json")
     if not os.path.exists(cfg):
         return None
     with open(cfg) as f:
-        qc = json.load(f).get("quantization_config")
+        return json.load(f).get("quantization_config") or None
+
+
+def checkpoint_quantization(path: str) -> Optional[str]:
+    """What a checkpoint's ``config.json`` declares: ``"int4"`` for the AWQ format that is read
+    (``AWQ_SUPPORTED``), ``"fp8_block"`` for block-scaled FP8 (``FP8_BLOCK_SUPPORTED``; ``fmt`` and
+    ``activation_scheme`` may be absent), None without ``quantization_config``.  Every other declared
+    format — other methods (all of GPTQ), bit widths, group sizes, versions, per-tensor FP8, static
+    activation scales, other block sizes — is a ValueError."""
+    qc = _quantization_config(path)
     if not qc:
         return None
-    ok = (str(qc.get("quant_method", "")).lower() == "awq" and qc.get("bits") == 4 and qc.get("group_size") == 128
-          and qc.get("zero_point") is True and str(qc.get("version", "")).lower() == "gemm")
-    if not ok:
-        shown = {k: qc.get(k) for k in ("quant_method", "bits", "group_size", "zero_point", "version")}
-        raise ValueError(f"{path}: unsupported quantization_config {shown}; the only pre-quantised checkpoints "
-                         f"read are {AWQ_SUPPORTED}")
-    return "int4"
+    method = str(qc.get("quant_method", "")).lower()
+    if method == "fp8":
+        block = qc.get("weight_block_size")
+        if (str(qc.get("fmt", "e4m3")).lower() == "e4m3" and block is not None and list(block) == [128, 128]
+                and str(qc.get("activation_scheme", "dynamic")).lower() == "dynamic"):
+            return "fp8_block"
+        keys = ("quant_method", "fmt", "weight_block_size", "activation_scheme")
+    else:
+        if (method == "awq" and qc.get("bits") == 4 and qc.get("group_size") == 128 and qc.get("zero_point") is True
+                and str(qc.get("version", "")).lower() == "gemm"):
+            return "int4"
+        keys = ("quant_method", "bits", "group_size", "zero_point", "version")
+    shown = {k: qc.get(k) for k in keys}
+    raise ValueError(f"{path}: unsupported quantization_config {shown}; the only pre-quantised checkpoints "
+                     f"read are {AWQ_SUPPORTED}, and {FP8_BLOCK_SUPPORTED}")
+
+
+def _not_converted(path: str) -> tuple:
+    """``modules_to_not_convert`` of the checkpoint's quantization_config: layers kept in bf16."""
+    return tuple((_quantization_config(path) or {}).get("modules_to_not_convert") or ())
+
+
+def _read_fp8_block(rd: CheckpointReader, names, slot, device, keep_bf16=()):
+    """The ``Fp8BlockWeight`` of the block-FP8 linear layers ``names`` (without suffix), concatenated
+    along N, for a model slot of that shape: each ``weight`` / ``weight_scale_inv`` pair has its block
+    rows expanded to 16-row tiles on the CPU, then moves.  Layers the checkpoint lists in
+    ``modules_to_not_convert`` are bf16 there and are copied into the slot, which stays a tensor —
+    all of a fused slot's parts or none; a bf16 weight that is not listed is an error."""
+    from dgi import ops
+    listed = [any(n == m or n.startswith(m + ".") or n.endswith("." + m) for m in keep_bf16) for n in names]
+    if all(listed):
+        r0 = 0
+        for name in names:
+            t = rd.read(name + ".weight")
+            _put(slot[r0:r0 + t.shape[0]], t)
+            r0 += t.shape[0]
+        if r0 != slot.shape[0]:
+            raise ValueError(f"checkpoint tensors {list(names)} give {r0} rows != model slot {tuple(slot.shape)}")
+        return slot
+    if any(listed):
+        raise ValueError(f"{rd.path}: {list(names)} share one fused projection, but only some of them are in "
+                         "modules_to_not_convert")
+    parts = []
+    for name in names:
+        if f"{name}.weight" not in rd:
+            raise KeyError(f"{rd.path}: FP8 checkpoint without {name}.weight")
+        w = rd.read(name + ".weight")
+        if w.dtype != torch.float8_e4m3fn or f"{name}.weight_scale_inv" not in rd:
+            raise ValueError(f"{rd.path}: {name}.weight is {w.dtype} with"
+                             f"{'' if f'{name}.weight_scale_inv' in rd else 'out'} a weight_scale_inv; a block-FP8 "
+                             "checkpoint holds float8_e4m3fn weights with scales for every linear layer that "
+                             "modules_to_not_convert does not list")
+        try:
+            parts.append(ops.fp8_block_from_hf(w, rd.read(name + ".weight_scale_inv")))
+        except ValueError as e:
+            raise ValueError(f"{rd.path}: {name}: {e}") from None
+    w = ops.fp8_block_cat(parts)
+    if tuple(w.shape) != tuple(slot.shape):
+        raise ValueError(f"checkpoint tensors {list(names)} give shape {tuple(w.shape)} != model slot {tuple(slot.shape)}")
+    return ops.Fp8BlockWeight(w.q.to(device), w.scale.to(device))
 
 
 def _read_awq(rd: CheckpointReader, names, slot, device):
@@ -181,10 +245,22 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
     ``ops.Int4Weight`` repacked from ``*.qweight`` / ``*.qzeros`` / ``*.scales`` and leaves the model
     with ``weight_quant == "int4"``; everything else in it is read as usual.  Pipeline stages read
     their layers; tensor parallelism would slice inside packed words and quantisation groups and
-    is refused."""
+    is refused.
+
+    A block-FP8 checkpoint (``"fp8_block"``) fills them with ``ops.Fp8BlockWeight`` from ``*.weight``
+    / ``*.weight_scale_inv`` and leaves ``weight_quant == "fp8"``; layers in ``modules_to_not_convert``
+    (the LM head of the published files) are read as bf16.  Refused: tensor parallelism, MoE models,
+    a K that is no multiple of 128, and — in ``quantize_weights`` — ``act_quant="fp8"``."""
     if hasattr(model, "_check_not_quantised"):     # the loader writes the bf16 tensors in place
         model._check_not_quantised("load_checkpoint")
-    awq = checkpoint_quantization(path) == "int4"
+    declared = checkpoint_quantization(path)
+    awq, fp8b = declared == "int4", declared == "fp8_block"
+    if fp8b and tp > 1:
+        raise ValueError(f"{path}: tensor parallelism over a block-FP8 checkpoint is not supported (tp={tp}): a "
+                         "rank's slice would cut scale blocks; serve it on one GPU or over pipeline stages")
+    if fp8b and model.cfg.is_moe:
+        raise ValueError(f"{path}: block-FP8 checkpoints of MoE models are not supported (no block-scaled experts)")
+    keep = _not_converted(path) if fp8b else ()
     if awq and tp > 1:
         raise ValueError(f"{path}: tensor parallelism over an AWQ checkpoint is not supported (tp={tp}); "
                          "serve it on one GPU or over pipeline stages")
@@ -207,6 +283,8 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
         a = p + "self_attn."
         if awq:
             L.qkv = _read_awq(rd, [a + "q_proj", a + "k_proj", a + "v_proj"], L.qkv, model.device)
+        elif fp8b:
+            L.qkv = _read_fp8_block(rd, [a + "q_proj", a + "k_proj", a + "v_proj"], L.qkv, model.device, keep)
         else:
             _put(L.qkv[:ql], rd.read(a + "q_proj.weight", rows=q_rows))
             _put(L.qkv[ql:ql + kl], rd.read(a + "k_proj.weight", rows=kv_rows))
@@ -226,12 +304,17 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
             n += 2
         if awq:
             L.o = _read_awq(rd, [a + "o_proj"], L.o, model.device)
+        elif fp8b:
+            L.o = _read_fp8_block(rd, [a + "o_proj"], L.o, model.device, keep)
         else:
             _put(L.o, rd.read(a + "o_proj.weight", cols=q_rows) if tp > 1 else rd.read(a + "o_proj.weight"))
         m = p + "mlp."
         if awq:
             L.gate_up = _read_awq(rd, [m + "gate_proj", m + "up_proj"], L.gate_up, model.device)
             L.down = _read_awq(rd, [m + "down_proj"], L.down, model.device)
+        elif fp8b:
+            L.gate_up = _read_fp8_block(rd, [m + "gate_proj", m + "up_proj"], L.gate_up, model.device, keep)
+            L.down = _read_fp8_block(rd, [m + "down_proj"], L.down, model.device, keep)
         elif L.router is not None:
             # Qwen3-MoE: the published per-expert tensors, each read straight into its slice of the
             # stacked [E, 2I, H] / [E, H, I] weights (never a CPU copy of a whole layer's experts)
@@ -255,7 +338,7 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
         else:
             _put(L.gate_up[:Il], rd.read(m + "gate_proj.weight", rows=i_rows))
             _put(L.gate_up[Il:], rd.read(m + "up_proj.weight", rows=i_rows))
-        if L.router is None and not awq:
+        if L.router is None and not awq and not fp8b:
             _put(L.down, rd.read(m + "down_proj.weight", cols=i_rows) if tp > 1 else rd.read(m + "down_proj.weight"))
         _put(L.in_norm, rd.read(p + "input_layernorm.weight"))
         _put(L.post_norm, rd.read(p + "post_attention_layernorm.weight"))
@@ -272,9 +355,12 @@ def load_checkpoint(model, path: str, tp_rank: int = 0, tp: int = 1) -> dict:
             else:   # tied checkpoint served by an untied slot (last stage without the embedding)
                 _put(model.lm_head, rd.read("model.embed_tokens.weight"))
             n += 1
-    if awq:
+    if awq or fp8b:
         from dgi import ops
-        model._adopt_quantised("int4", ops.Int4Weight)
+        if awq:
+            model._adopt_quantised("int4", ops.Int4Weight)
+        else:
+            model._adopt_quantised("fp8", ops.Fp8BlockWeight)
         if model.device.type == "cuda":
             torch.cuda.empty_cache()      # the empty bf16 projections the packed ones replaced
     # per-layer KV-cache scales, used only by an fp8 KV pool (``EngineConfig.kv_dtype``)

@@ -21,6 +21,8 @@ import torch
 
 from dgi.ops.fp8 import E4M3_MAX, Fp8Weight, quantize_fp8  # noqa: F401  (public: ops.Fp8Weight, ops.quantize_fp8)
 from dgi.ops.fp8 import Fp8ExpertWeight, quantize_fp8_experts  # noqa: F401  (public: the MoE experts' container)
+from dgi.ops.fp8 import (Fp8BlockWeight, fp8_block_cat, fp8_block_from_hf,  # noqa: F401  (public: block-scaled checkpoints)
+                         quantize_fp8_block_hf)
 from dgi.ops.mxfp4 import Mxfp4Weight, quantize_mxfp4  # noqa: F401  (public: ops.Mxfp4Weight, ops.quantize_mxfp4)
 from dgi.ops.int4 import (Int4ExpertWeight, Int4Weight, int4_cat, int4_from_awq, quantize_int4,  # noqa: F401  (public)
                           quantize_int4_experts)
@@ -746,6 +748,35 @@ def _linear_fp8(x: torch.Tensor, w: Fp8Weight, bias: Optional[torch.Tensor], out
     return r
 
 
+# Block-scaled FP8 projections (Fp8BlockWeight: the 128 x 128-scale checkpoints).  The routing is
+# _linear_fp8's without W8A8 (the e4m3 x e4m3 GEMM takes per-channel scales): skinny_gemm_w8b for the
+# decode-sized steps, on skinny_gemm_w8's launch configs (the bytes per step are the same), and
+# dequant_fp8_block + the bf16 GEMM for everything else.
+def linear_fp8_block_ref(x: torch.Tensor, w: Fp8BlockWeight, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return torch.nn.functional.linear(x.float(), w.dequant(torch.float32),
+                                      None if bias is None else bias.float()).to(x.dtype)
+
+
+def dequant_fp8_block(w: Fp8BlockWeight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] copy of a block-scaled fp8 weight; ``out``: a flat bf16 buffer of >= N*K elements."""
+    return _dequant("dequant_fp8_block", w, out)
+
+
+def _linear_fp8_block(x: torch.Tensor, w: Fp8BlockWeight, bias: Optional[torch.Tensor], out: Optional[torch.Tensor]):
+    if x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16:
+        M, K = x.shape
+        N = w.shape[0]
+        if _use_skinny_quant(M, N, K) and _skinny_takes(x):
+            return _skinny_run("skinny_gemm_w8b", x, N, out, w.q, w.scale, bias, _skinny_w8_cfg(M, N))
+        r = torch.nn.functional.linear(x, dequant_fp8_block(w, w.scratch), bias)
+    else:
+        r = linear_fp8_block_ref(x, w, bias)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
 # MXFP4 weight-only projections (skinny_gemm_mxfp4.hip).  The W4A16 kernel takes every decode-sized
 # step it can launch, as the fp8 kernel does: M <= 32, K % 1024 == 0, N % 16 == 0.  Everything else
 # is dequantised to bf16 (dequant_mxfp4) and runs the bf16 GEMM.  Every mxfp4 value is a bf16 number,
@@ -886,9 +917,11 @@ def _linear_int4(x: torch.Tensor, w: Int4Weight, bias: Optional[torch.Tensor], o
 def linear(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w.T (+ bias) for a 2-D activation; [N, K] weights as stored (bf16 tensor, ``Fp8Weight``,
-    ``Mxfp4Weight`` or ``Int4Weight``)."""
+    ``Fp8BlockWeight``, ``Mxfp4Weight`` or ``Int4Weight``)."""
     if isinstance(w, Fp8Weight):
         return _linear_fp8(x, w, bias, out)
+    if isinstance(w, Fp8BlockWeight):
+        return _linear_fp8_block(x, w, bias, out)
     if isinstance(w, Mxfp4Weight):
         return _linear_mxfp4(x, w, bias, out)
     if isinstance(w, Int4Weight):

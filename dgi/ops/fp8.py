@@ -58,6 +58,104 @@ class Fp8Weight:
         return f"Fp8Weight(shape={tuple(self.q.shape)}, device={self.q.device})"
 
 
+FP8_BLOCK_ROWS, FP8_BLOCK_K = 16, 128     # one scale per 16-row kernel tile and 128-deep K step
+
+
+class Fp8BlockWeight:
+    """Block-scaled FP8, the format of the published FP8 checkpoints (``weight_block_size``
+    [128, 128]) as the kernel reads it: ``q`` [N, K] e4m3 codes, ``scale`` [N/16, K/128] fp32, and
+    the weight is ``q[n, k] * scale[n // 16, k // 128]``.  The checkpoint's 128-row blocks are
+    expanded to 16-row tiles once at load (``fp8_block_from_hf``; N*K/512 bytes): tensors
+    concatenated along N stay right when a part's N is no multiple of 128, a wave's scales are one
+    contiguous run along K, and the kernel divides nothing.  No code is ever rounded again."""
+    __slots__ = ("q", "scale", "scratch")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor, scratch: Optional[torch.Tensor] = None):
+        if q.dtype != torch.float8_e4m3fn or q.dim() != 2 or not q.is_contiguous():
+            raise ValueError("Fp8BlockWeight: q must be a contiguous [N, K] float8_e4m3fn tensor")
+        N, K = q.shape
+        if N % FP8_BLOCK_ROWS or K % FP8_BLOCK_K:
+            raise ValueError(f"Fp8BlockWeight: N % 16 == 0 and K % 128 == 0, got [{N}, {K}]")
+        if (scale.dtype != torch.float32 or scale.shape != (N // FP8_BLOCK_ROWS, K // FP8_BLOCK_K)
+                or not scale.is_contiguous()):
+            raise ValueError("Fp8BlockWeight: scale must be a contiguous [N/16, K/128] float32 tensor")
+        if scale.device != q.device:
+            raise ValueError("Fp8BlockWeight: q and scale on one device")
+        self.q = q
+        self.scale = scale
+        # flat bf16 buffer of >= N*K elements for the dequantised copy, as Fp8Weight's
+        self.scratch = scratch
+
+    @property
+    def shape(self) -> torch.Size:
+        return self.q.shape
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    def nbytes(self) -> int:
+        return self.q.numel() + 4 * self.scale.numel()
+
+    def dequant(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """``q * scale`` of its block in fp32, rounded once to ``dtype``."""
+        N, K = self.q.shape
+        out = torch.empty(N, K, dtype=dtype, device=self.q.device)
+        step = max(16, ((64 << 20) // max(1, K)) // 16 * 16)      # bounded fp32 temporaries
+        for r0 in range(0, N, step):
+            qf = self.q[r0:r0 + step].float().view(-1, FP8_BLOCK_ROWS, K // FP8_BLOCK_K, FP8_BLOCK_K)
+            s = self.scale[r0 // 16:(r0 + step) // 16]
+            out[r0:r0 + step] = (qf * s[:, None, :, None]).view(-1, K).to(dtype)
+        return out
+
+    def __repr__(self) -> str:
+        return f"Fp8BlockWeight(shape={tuple(self.q.shape)}, device={self.q.device})"
+
+
+def fp8_block_from_hf(weight: torch.Tensor, weight_scale_inv: torch.Tensor, block=(128, 128)) -> Fp8BlockWeight:
+    """One linear layer of a block-FP8 checkpoint: ``weight`` [N, K] e4m3 and ``weight_scale_inv``
+    [ceil(N/128), ceil(K/128)] fp32, with ``w = weight * weight_scale_inv`` of the element's block.
+    The block rows are repeated for the eight 16-row tiles they cover (the last block row may be
+    partial); the codes are kept as they are."""
+    if tuple(block) != (128, 128):
+        raise ValueError(f"fp8_block_from_hf: weight_block_size {list(block)} is not supported, only [128, 128]")
+    if weight.dtype != torch.float8_e4m3fn or weight.dim() != 2:
+        raise ValueError("fp8_block_from_hf: weight must be a 2-D float8_e4m3fn tensor")
+    if weight_scale_inv.dtype != torch.float32:
+        raise ValueError("fp8_block_from_hf: weight_scale_inv must be float32")
+    N, K = weight.shape
+    if N % FP8_BLOCK_ROWS or K % FP8_BLOCK_K:
+        raise ValueError(f"fp8_block_from_hf: a [{N}, {K}] weight; the kernel's layout needs N % 16 == 0 and "
+                         f"K % 128 == 0")
+    if tuple(weight_scale_inv.shape) != ((N + 127) // 128, K // 128):
+        raise ValueError(f"fp8_block_from_hf: weight_scale_inv is {tuple(weight_scale_inv.shape)}, a [{N}, {K}] "
+                         f"weight has [{(N + 127) // 128}, {K // 128}] blocks")
+    scale = weight_scale_inv.repeat_interleave(128 // FP8_BLOCK_ROWS, dim=0)[:N // FP8_BLOCK_ROWS]
+    return Fp8BlockWeight(weight.contiguous(), scale.contiguous())
+
+
+def quantize_fp8_block_hf(w: torch.Tensor):
+    """``(weight, weight_scale_inv)`` of a [N, K] weight in the checkpoint format ``fp8_block_from_hf``
+    reads: symmetric e4m3 per 128 x 128 block, ``scale = max|block| / 448`` (1 for a zero block), the
+    last block row and column partial where N or K is no multiple of 128.  For writing test and
+    benchmark checkpoints; serving never quantises to this format."""
+    N, K = w.shape
+    nb, kb = (N + 127) // 128, (K + 127) // 128
+    wf = torch.zeros(nb * 128, kb * 128, dtype=torch.float32, device=w.device)
+    wf[:N, :K] = w.float()
+    blocks = wf.view(nb, 128, kb, 128)
+    amax = blocks.abs().amax(dim=(1, 3))
+    scale = torch.where(amax > 0, amax / E4M3_MAX, torch.ones_like(amax))
+    q = (blocks / scale[:, None, :, None]).clamp_(-E4M3_MAX, E4M3_MAX).view(nb * 128, kb * 128)[:N, :K]
+    return q.contiguous().to(torch.float8_e4m3fn), scale.contiguous()
+
+
+def fp8_block_cat(parts) -> Fp8BlockWeight:
+    """Concatenate along N (q|k|v, gate|up): every 16-row tile carries its own scales."""
+    q = torch.cat([p.q.view(torch.uint8) for p in parts], 0).view(torch.float8_e4m3fn)      # bytes: nothing converts
+    return Fp8BlockWeight(q, torch.cat([p.scale for p in parts], 0))
+
+
 class Fp8ExpertWeight:
     """The experts of a MoE layer, FP8 weight-only: ``q`` [E, N, K] e4m3 codes, ``scale`` [E, N]
     fp32 (one per expert and output channel); expert e's weight is ``q[e] * scale[e][:, None]``.

@@ -34,14 +34,28 @@ def main():
     ap.add_argument("--expert-quant", default=None, choices=["fp8", "awq"],
                     help="MoE models: weight-only experts, fp8 (e4m3) or awq (int4, group scales and zero points)")
     ap.add_argument("--num-blocks", type=int, default=None, help="KV pages (default: from free memory)")
+    ap.add_argument("--fp8-block", action="store_true",
+                    help="with --weight-quant fp8: the containers a block-FP8 checkpoint (128 x 128 scales) loads into, "
+                         "made in memory from the seeded model's weights as such a checkpoint's tensors would be")
     a = ap.parse_args()
     cfg = EngineConfig(model=a.model, device="cuda", max_num_seqs=max(a.batch), max_num_batched_tokens=8192,
                        max_model_len=max(2048, a.prefill_tokens + 64), kv_fraction=0.5, weight_quant=a.weight_quant,
                        act_quant=a.act_quant,
                        kv_dtype=a.kv_dtype, num_blocks=a.num_blocks, expert_quant=a.expert_quant)
-    eng = LLMEngine(cfg)
+    model = None
+    if a.fp8_block:
+        from dgi import ops
+        from dgi.models.config import get_config
+        from dgi.models.llama import QUANT_SLOTS, LlamaModel
+        model = LlamaModel(get_config(a.model), "cuda", seed=cfg.seed)
+        for L in model.layers:
+            for k in QUANT_SLOTS:
+                setattr(L, k, ops.fp8_block_from_hf(*ops.quantize_fp8_block_hf(getattr(L, k))))
+        model._adopt_quantised("fp8", ops.Fp8BlockWeight)
+        torch.cuda.empty_cache()
+    eng = LLMEngine(cfg, model_cfg=model.cfg if model else None, model=model)
     print(json.dumps({"model": a.model, "weight_quant": a.weight_quant, "act_quant": a.act_quant, "kv_dtype": a.kv_dtype,
-                      "expert_quant": a.expert_quant, "weight_bytes": eng.model.weight_bytes(),
+                      "fp8_block": a.fp8_block, "expert_quant": a.expert_quant, "weight_bytes": eng.model.weight_bytes(),
                       "num_blocks": eng.pool.num_blocks}), flush=True)
     eng.warmup()
     g = torch.Generator().manual_seed(0)
@@ -67,7 +81,7 @@ def main():
         while eng.has_unfinished():
             eng.step()
         rows.append({"model": a.model, "batch": B, "tpot_ms": round(ms, 3), "tok_s": round(B / ms * 1000, 1), "weight_quant": a.weight_quant,
-                     "act_quant": a.act_quant, "kv_dtype": a.kv_dtype, "expert_quant": a.expert_quant,
+                     "fp8_block": a.fp8_block, "act_quant": a.act_quant, "kv_dtype": a.kv_dtype, "expert_quant": a.expert_quant,
                      "skinny_max_m": int(os.environ.get("DGI_SKINNY_MAX_M", "32")), "host_phases_ms": ph})
         print(json.dumps(rows[-1]), flush=True)
     if a.prefill_tokens > 0:

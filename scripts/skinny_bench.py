@@ -9,8 +9,11 @@ adds the W8A16 kernel (``skinny_gemm_w8``, e4m3 weights at half the bytes) as
 ``fp8_c<cfg>`` columns, over the same number of rotating copies; ``--w4-cfg`` the
 W4A16 kernel (``skinny_gemm_w4``, MXFP4 weights at a quarter of the bytes plus one scale
 byte per 32 elements) as ``w4_c<cfg>``; ``--i4-cfg`` the INT4 kernel (``skinny_gemm_i4``, 4-bit codes
-plus four bytes of scale and zero point per 128 elements) as ``i4_c<cfg>``.  ``-1`` in any of the
-lists stands for the config the ops layer picks for the shape and row count.
+plus four bytes of scale and zero point per 128 elements) as ``i4_c<cfg>``; ``--fp8b-cfg`` the
+block-scaled W8A16 kernel (``skinny_gemm_w8b``, the same codes under one fp32 scale per 16 x 128 block)
+as ``fp8b_c<cfg>``.  ``-1`` in any of the lists stands for the config the ops layer picks for the shape
+and row count.  ``--repeat R`` times every implementation R times, alternating between them, and
+reports the median with the smallest and largest time: the spread a ratio has to be read against.
 """
 import argparse
 import json
@@ -71,6 +74,8 @@ def main():
     ap.add_argument("--fp8-cfg", type=int, nargs="*", default=[0], help="skinny_gemm_w8 launch configs (none: skip)")
     ap.add_argument("--w4-cfg", type=int, nargs="*", default=[], help="skinny_gemm_w4 launch configs (none: skip)")
     ap.add_argument("--i4-cfg", type=int, nargs="*", default=[], help="skinny_gemm_i4 launch configs (none: skip)")
+    ap.add_argument("--fp8b-cfg", type=int, nargs="*", default=[], help="skinny_gemm_w8b launch configs (none: skip)")
+    ap.add_argument("--repeat", type=int, default=1, help="timings per implementation, alternating (median reported)")
     ap.add_argument("--no-hipblaslt", action="store_true")
     ap.add_argument("--graph", action="store_true", help="time hipGraph replays instead of eager launches")
     ap.add_argument("--out", default=None)
@@ -84,6 +89,7 @@ def main():
         qs = [ops.quantize_fp8(w) for w in ws] if a.fp8_cfg else []
         q4 = [ops.quantize_mxfp4(w) for w in ws] if a.w4_cfg else []
         i4 = [ops.quantize_int4(w) for w in ws] if a.i4_cfg else []
+        qb = [ops.fp8_block_from_hf(*ops.quantize_fp8_block_hf(w)) for w in ws] if a.fp8b_cfg else []
         for M in a.ms:
             x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
             out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
@@ -106,6 +112,11 @@ def main():
                 if ops.skinny_i4_cfg_ok(pick, N, K):
                     impls["i4_pick" if c < 0 else f"i4_c{c}"] = (lambda c_: lambda i: torch.ops.dgi.skinny_gemm_i4(
                         out, x, i4[i % copies].q, i4[i % copies].sz, None, c_))(pick)
+            for c in a.fp8b_cfg:
+                pick = ops._skinny_w8_cfg(M, N) if c < 0 else c
+                if ops.skinny_w8_cfg_ok(pick, N, K):
+                    impls["fp8b_pick" if c < 0 else f"fp8b_c{c}"] = (lambda c_: lambda i: torch.ops.dgi.skinny_gemm_w8b(
+                        out, x, qb[i % copies].q, qb[i % copies].scale, None, c_))(pick)
             ref = F.linear(x.float(), ws[0].float())
             torch.ops.dgi.skinny_gemm(out, x, ws[0], None, 0)
             err = (out.float() - ref).abs().max().item()
@@ -124,21 +135,40 @@ def main():
                 torch.ops.dgi.skinny_gemm_i4(out, x, i4[0].q, i4[0].sz, None, 0)
                 erri = (out.float() - F.linear(x.float(), i4[0].dequant())).abs().max().item()
                 rmsi = ((out.float() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
-            for impl, fn in impls.items():
-                us = timed(fn, a.iters, a.graph)
-                fp8, w4, wi = impl.startswith("fp8"), impl.startswith("w4"), impl.startswith("i4")
-                nbytes = qs[0].nbytes() if fp8 else q4[0].nbytes() if w4 else i4[0].nbytes() if wi else N * K * 2
+            errb = rmsb = rms8 = None
+            if a.fp8b_cfg:
+                torch.ops.dgi.skinny_gemm_w8b(out, x, qb[0].q, qb[0].scale, None, 0)
+                errb = (out.float() - F.linear(x.float(), qb[0].dequant())).abs().max().item()
+                rmsb = ((out.float() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
+                if a.fp8_cfg:     # the per-channel format's cost beside it
+                    torch.ops.dgi.skinny_gemm_w8(out, x, qs[0].q, qs[0].scale, None, 0)
+                    rms8 = ((out.float() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
+            times = {impl: [] for impl in impls}
+            for _ in range(max(1, a.repeat)):
+                for impl, fn in impls.items():
+                    times[impl].append(timed(fn, a.iters, a.graph))
+            for impl in impls:
+                ts = sorted(times[impl])
+                us = ts[len(ts) // 2]
+                fpb = impl.startswith("fp8b")
+                fp8, w4, wi = impl.startswith("fp8") and not fpb, impl.startswith("w4"), impl.startswith("i4")
+                nbytes = (qs[0].nbytes() if fp8 else qb[0].nbytes() if fpb else q4[0].nbytes() if w4
+                          else i4[0].nbytes() if wi else N * K * 2)
                 rows.append({"shape": name, "M": M, "N": N, "K": K, "impl": impl, "us": round(us, 2),
                              "weight_TBs": round(nbytes / us / 1e6, 2),
-                             "max_err": round(err8 if fp8 else err4 if w4 else erri if wi else err, 4),
+                             "max_err": round(err8 if fp8 else errb if fpb else err4 if w4 else erri if wi else err, 4),
                              "timing": "graph" if a.graph else "eager"})
+                if a.repeat > 1:
+                    rows[-1]["us_min"], rows[-1]["us_max"] = round(ts[0], 2), round(ts[-1], 2)
+                if fpb or (fp8 and rms8 is not None):
+                    rows[-1]["rel_rms_vs_bf16"] = round(rmsb if fpb else rms8, 5)
                 if w4 or wi:
                     rows[-1]["rel_rms_vs_bf16"] = round(rms4 if w4 else rmsi, 4)
                 if impl.endswith("_pick"):
-                    rows[-1]["cfg"] = (ops._skinny_w8_cfg(M, N) if fp8 else ops._skinny_w4_cfg(M, N, K) if w4
+                    rows[-1]["cfg"] = (ops._skinny_w8_cfg(M, N) if fp8 or fpb else ops._skinny_w4_cfg(M, N, K) if w4
                                        else ops._skinny_i4_cfg(M, N, K))
                 print(json.dumps(rows[-1]), flush=True)
-        del ws, qs, q4, i4
+        del ws, qs, q4, i4, qb
         torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "w") as f:

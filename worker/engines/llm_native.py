@@ -15,7 +15,8 @@ Config keys accepted (SURVEY Appendix C mapping): ``model_id``, ``device``,
 ``max_running_requests``/``max_num_seqs``, ``chunked_prefill_size``,
 ``enable_prefix_caching``, ``context_length``/``max_model_len``,
 ``num_blocks``, ``use_graphs``/``enforce_eager``, ``quantization``/``weight_quant``
-(``"fp8"``: weight-only e4m3 projections, ``"mxfp4"``: weight-only OCP MXFP4 projections, ``"awq"``:
+(``"fp8"``: weight-only e4m3 projections — a block-scaled FP8 checkpoint, ``weight_block_size`` [128, 128], is
+served from its own codes and scales with this value or none, and refuses any other; ``"mxfp4"``: weight-only OCP MXFP4 projections, ``"awq"``:
 weight-only 4-bit projections with group scales and zero points, read from an AWQ checkpoint or rounded from bf16;
 anything else is served unquantised), ``act_quant`` (``"fp8"`` on top of it: W8A8 for steps of at least
 ``DGI_W8A8_MIN_M`` rows, default 2048; ``quantization: "fp8"`` alone stays W8A16), ``expert_quant`` (``"fp8"``:
@@ -111,6 +112,12 @@ class NativeLLMEngine(LLMBaseEngine):
         quant = c.get("weight_quant", c.get("quantization"))
         if quant is not None and str(quant).lower() in ("", "none"):
             quant = None
+        if ckpt is not None:
+            # a block-FP8 checkpoint (128 x 128 scales) is served as it is: its format is the only one it has
+            from dgi.models.weights import checkpoint_quantization
+            if checkpoint_quantization(ckpt) == "fp8_block" and quant is not None and str(quant).lower() != "fp8":
+                raise ValueError(f"quantization={quant!r}: {ckpt} is a block-scaled FP8 checkpoint; leave "
+                                 "quantization unset or set it to 'fp8'")
         if quant is not None and str(quant).lower() not in ("fp8", "mxfp4", "awq"):
             logger.warning("quantization=%r is not supported by the native engine (supported: 'fp8', 'mxfp4', "
                            "'awq', weight-only); serving %s unquantised", quant, model_id)
